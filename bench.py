@@ -19,11 +19,20 @@ collective; the decoded lists are gathered on rank 0 through sharding.gather_res
 timed region.  Weak scaling by default (fixed reads per GPU); `--total-reads T` fixes the job instead
 (strong scaling, configs[2]'s shape: rank r takes reads r, r+N, ...).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+Prints ONE JSON line on rank 0 with extra objects:
   roofline      algorithmic bytes (SURVEY 8d formula) / HIP-event time of the dominant kernel, measured live
                 on the decoder's stream around every launch, against the 8 TB/s HBM peak
+A plain run does only that: set-up, warm-up, the --steps timed steps, the result line.  `--full` adds what
+runs after the timed region:
+  cross_check   every list of the last timed batch against kernel mode 1 (--no-cross-check drops it)
+  extra_configs configs[3] and configs[4], one short driver-timed run each (--no-extra-configs drops them)
   cpu_baseline  the unmodified reference binary (oracle/_ref) on this host, all (<=16) OpenMP threads, on a
                 bounded sample of the same reads; cpu_baseline_single_thread: the same with -t 1
+                (--no-cpu-baseline drops them)
+
+`--dump-outputs DIR` (rank 0): the lists of the last timed step, in global read order, as float32 .npy files
+(counts, msgs, scores, read_index; a fixed seeded sample of the reads when all of them would exceed 64 MB).
+The reads are seeded, so the same arguments give the same inputs on every run and every build.
 """
 import argparse
 import json
@@ -63,6 +72,9 @@ def parse(argv=None):
     ap.add_argument("--dump-lists", type=str, default="", help="rank 0 writes the gathered lists of the last step (npz)")
     ap.add_argument("--no-extra-configs", action="store_true", help="skip the short driver-timed runs of configs[3] and configs[4]")
     ap.add_argument("--extra-reads", type=int, default=32, help="reads per extra configuration")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the cross-check, the extra configurations and the CPU baseline after the timed region")
+    ap.add_argument("--dump-outputs", type=str, default="", help="rank 0 writes the lists of the last timed step as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -169,6 +181,24 @@ def run_extra_config(pkg, synth, np, name, m, r, L, golden, n_reads, devno, buil
             "golden_checked": list(golden), "kernel_mode": p["kernel"], "slots": p["slots"], "build_id": build_id}
 
 
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(path, gathered, list_size, msg_len):
+    """What a caller of the timed path receives for the last timed step, as float32 arrays: counts[n] (list length, or the
+    read's negative error code), msgs[n, L, msg_len] (0/1), scores[n, L] (0 past the list's end) and read_index[n] (global
+    read index).  Above DUMP_LIMIT bytes, a sample of the reads drawn with a fixed seed (sorted, so still in read order)."""
+    import numpy as np
+    from nanopore_dna_storage_amd import sharding
+    n = len(gathered)
+    keep = max(1, (DUMP_LIMIT - 4096) // (4 * (2 + list_size + list_size * msg_len)))     # (4096: the .npy headers)
+    idx = np.arange(n) if n <= keep else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    c, m_, s_ = sharding.pack_results([gathered[int(i)] for i in idx], list_size, msg_len)
+    os.makedirs(path, exist_ok=True)
+    for name, arr in (("counts", c), ("msgs", m_), ("scores", s_), ("read_index", idx)):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+
+
 def main():
     a = parse()
     in_group = "WORLD_SIZE" in os.environ
@@ -235,7 +265,7 @@ def main():
 
     # ---- CPU leg: set up here, run AFTER the timed region (nothing but the decoder's host thread works during it) ----
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
         from oracle import oracle as O
         import tempfile
         cpu = dict(O=O, tmp=tempfile.mkdtemp(prefix="lva_bench_"))
@@ -307,6 +337,8 @@ def main():
         if a.dump_lists:
             c, m_, s_ = sharding.pack_results(gathered, a.list_size, a.msg_len)
             np.savez(a.dump_lists, counts=c, msgs=m_, scores=s_)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, gathered, a.list_size, a.msg_len)
         total_reads = n_global * a.steps
         nblk_mean = float(np.mean([x["post"].shape[0] for x in reads]))
         distinct = min(len(pool_idx), per_step * (a.steps + a.warmup)) if not strong else per_step
@@ -392,7 +424,7 @@ def main():
         }
         # ---- every list of one timed batch against an independent exact kernel (mode 1: one thread per target, the
         #      reference merge verbatim, no fingerprints, no lazy messages), outside the timed region ----
-        if not a.no_cross_check and prof["kernel"] != 1:
+        if a.full and not a.no_cross_check and prof["kernel"] != 1:
             t1 = time.time()
             # (a second decoder beside the first: both keep their read slots in HBM -- 2 x 44 GB at the benchmark shape)
             with pkg.Decoder(a.mem_conv, a.rate, a.msg_len, list_size=a.list_size, max_deviation=a.max_deviation,
@@ -416,7 +448,7 @@ def main():
                 "all" if k == len(bt["reads"]) else "the first", len(want), time.time() - t1)
         # ---- configs[3] and configs[4] of BASELINE.json, one short driver-timed run each at the decoder's default slot count (the
         #      headline decoder is closed first: every decoder keeps its read slots resident in HBM) ----
-        if (world == 1 and not stub and not a.no_extra_configs
+        if (a.full and world == 1 and not stub and not a.no_extra_configs
                 and (a.mem_conv, a.rate, a.list_size, a.msg_len, a.max_deviation) == (M, RATE, LIST, MSG_LEN, MAXDEV)):
             if a.resident:
                 for bt in batches:

@@ -3,13 +3,17 @@
 (oracle/_ref/viterbi_nanopore.out, built by oracle/Makefile from /root/reference -- build container only, no GPU) and through
 oracle/lva_oracle.c, message lists compared line for line (the reference writes messages only; its exit code must agree too).
 
-    python scripts/fuzz_oracle_vs_reference.py SEED N [--threads 8]
+    python scripts/fuzz_oracle_vs_reference.py SEED N [--threads 8] [--record FILE | --recorded FILE]
+
+--record FILE writes the reference's exit code and lines of every case to FILE (JSON); --recorded FILE takes them from such
+a file instead, so that the same draw is checked where the binary is absent (where it exists it must agree with the file).
 
 Draws: m in {6, 8} (and 11 for one case in 25), every rate the code has, list sizes 1..70, bands down to max_deviation 1 and
 the unbanded default, both orientations, sync markers, substitutions / insertions / deletions, score ties (quantised posteriors),
 NaN and +inf posteriors, reads truncated to barely more blocks than trellis positions.
 """
 import argparse
+import json
 import os
 import sys
 import time
@@ -46,8 +50,18 @@ def main():
     ap.add_argument("seed", type=int)
     ap.add_argument("n", type=int)
     ap.add_argument("--threads", type=int, default=8)
+    ap.add_argument("--record", default="", help="write the reference's results of every case to this JSON file")
+    ap.add_argument("--recorded", default="", help="the reference's results of every case from this JSON file")
     a = ap.parse_args()
-    assert O.have_ref(), "build oracle/_ref first (make -C oracle ref): needs /root/reference"
+    live = O.have_ref()
+    rec = None
+    if a.recorded:
+        with open(a.recorded) as f:
+            rec = json.load(f)
+        assert (rec["seed"], len(rec["cases"])) == (a.seed, a.n), "the recording holds another draw"
+    assert live or rec is not None, "build oracle/_ref first (make -C oracle ref), or pass --recorded FILE"
+    assert live or not a.record, "--record needs the reference binary"
+    results = []
     rng = np.random.default_rng(a.seed)
     bad = 0
     t0 = time.time()
@@ -74,7 +88,15 @@ def main():
             if 1 <= keep < post.shape[0]:
                 post = post[:keep].copy()
                 what = " nblk=npos%+d" % (keep - npos)
-        code, lines = O.ref_decode(m, r, msg_len, post, L, md, rc=rc, num_threads=a.threads, **sync)
+        if live:
+            code, lines = O.ref_decode(m, r, msg_len, post, L, md, rc=rc, num_threads=a.threads, **sync)
+        if rec is not None:
+            want = rec["cases"][i]
+            if live and (code, lines) != (want["exit"], want["lines"]):
+                bad += 1
+                print("RECORDING DIFFERS from the reference binary in case %d" % i, flush=True)
+            code, lines = want["exit"], want["lines"]
+        results.append(dict(exit=code, lines=lines))
         try:
             msgs, _ = O.OracleCode(m, r, msg_len, rc=rc, **sync).decode(post, L, md, num_threads=a.threads)
             got = ["".join(map(str, x)) for x in msgs]
@@ -87,6 +109,9 @@ def main():
         print("%s m=%d r=%d msg_len=%d L=%d md=%s rc=%d margin=%.1f %s%s%s nblk=%d lines=%d exit=%d" % (
             "ok      " if ok else "MISMATCH", m, r, msg_len, L, md, rc, margin, kw or "", sync or "", what, post.shape[0], len(lines), code), flush=True)
     print("checked %d bad %d (%.0f s)" % (a.n, bad, time.time() - t0))
+    if a.record:
+        with open(a.record, "w") as f:
+            json.dump(dict(seed=a.seed, cases=results), f, separators=(",", ":"))
     return 1 if bad else 0
 
 

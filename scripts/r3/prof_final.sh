@@ -5,7 +5,7 @@
 #      restricted to the two lva_step_lazy instances so that the passes come back
 export TMPDIR=/tmp
 out=gpurun_out/r3prof; mkdir -p $out
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/trace.log 2>&1 || echo "trace failed"
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/trace.log 2>&1 || echo "trace failed"
 cat $out/trace/*/*kernel_stats.csv > $out/r3_default_kernel_stats.csv 2>/dev/null
 grep '^{' $out/trace.log | tail -1 > $out/r3_default_bench_under_trace.json
 B="python3 bench.py --steps 1 --warmup 0 --reads-per-step 64 --pool 64 --no-cpu-baseline --no-launch-events --no-cross-check"

@@ -6,7 +6,7 @@
 #   3. kernel traces of the other configurations
 export TMPDIR=/tmp
 out=gpurun_out/r5prof; mkdir -p $out
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/trace.log 2>&1 || echo "trace failed"
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/trace.log 2>&1 || echo "trace failed"
 cat $out/trace/*/*kernel_stats.csv > $out/r5_default_kernel_stats.csv 2>/dev/null
 grep '^{' $out/trace.log | tail -1 > $out/r5_default_bench_under_trace.json
 rm -rf $out/trace

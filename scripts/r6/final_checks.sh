@@ -7,7 +7,7 @@ timeout 600 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "xcd_aware
 timeout 500 python scripts/fuzz_gpu_vs_oracle.py 5602 140 > $out/fuzz_small.log 2>&1; tail -1 $out/fuzz_small.log
 timeout 300 python scripts/fuzz_m11.py 5603 8 > $out/fuzz_m11.log 2>&1; tail -1 $out/fuzz_m11.log
 grep -c MISMATCH $out/fuzz_small.log $out/fuzz_m11.log
-timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/r6f_driver_bench.json 2> $out/driver.err || tail -3 $out/driver.err
+timeout 900 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/r6f_driver_bench.json 2> $out/driver.err || tail -3 $out/driver.err
 python3 - <<PY
 import json
 j=json.loads(open("$out/r6f_driver_bench.json").read().strip().splitlines()[-1])

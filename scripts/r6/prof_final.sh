@@ -6,12 +6,12 @@
 # (profiles/r5_lazy128_pmc_summary.txt, r5_big64_pmc_summary.txt); scripts/r6/make_traffic_json.py derives profiles/r6_traffic.json.
 export TMPDIR=/tmp
 out=gpurun_out/r6prof; mkdir -p $out
-timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/trace.log 2>&1 || echo "trace failed"
+timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/trace.log 2>&1 || echo "trace failed"
 cat $out/trace/*/*kernel_stats.csv > $out/r6_default_kernel_stats.csv 2>/dev/null
 grep '^{' $out/trace.log | tail -1 > $out/r6_default_bench_under_trace.json
 rm -rf $out/trace
 head -6 $out/r6_default_kernel_stats.csv | cut -c1-60,150-230
-timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/r6_driver_bench.json 2> $out/driver.err || tail -3 $out/driver.err
+timeout 900 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/r6_driver_bench.json 2> $out/driver.err || tail -3 $out/driver.err
 python3 - <<PY
 import json
 j=json.loads(open("$out/r6_driver_bench.json").read().strip().splitlines()[-1])

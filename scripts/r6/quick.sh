@@ -9,7 +9,7 @@ fi
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-cross-check > $out/trace.log 2>&1 || echo "trace failed"
 cat $out/trace/*/*kernel_stats.csv > $out/kernel_stats.csv 2>/dev/null; rm -rf $out/trace
 head -8 $out/kernel_stats.csv | cut -d, -f1-5 | cut -c1-150
-python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --cross-check-reads 32 > $out/bench.json 2> $out/bench.err || tail -5 $out/bench.err
+python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --cross-check-reads 32 > $out/bench.json 2> $out/bench.err || tail -5 $out/bench.err
 python3 - <<PY
 import json
 j=json.loads(open("$out/bench.json").read().strip().splitlines()[-1])

@@ -34,16 +34,25 @@ def test_two_ranks_real_decoder_equal_single_process(tmp_path):
 
 
 def _bench(args, env_extra, tmp_path, tag):
+    """--full: the run also checks every list of its last timed batch against kernel mode 1 (an assert inside bench.py).
+    --dump-outputs writes the same lists as --dump-lists, as float32 .npy files."""
     dump = str(tmp_path / (tag + ".npz"))
+    outdir = str(tmp_path / (tag + "_out"))
     env = dict(os.environ, **env_extra)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-lists", dump], env=env,
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--full", "--dump-lists", dump, "--dump-outputs", outdir],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout
-    return json.loads(lines[0]), np.load(dump)
+    j, z = json.loads(lines[0]), np.load(dump)
+    assert "cross_check" in j["config"] or j["config"]["kernel"] == 1
+    for k in ("counts", "msgs", "scores"):
+        o = np.load(os.path.join(outdir, k + ".npy"))
+        assert o.dtype == np.float32 and np.array_equal(o, z[k].astype(np.float32)), k
+    assert np.array_equal(np.load(os.path.join(outdir, "read_index.npy")), np.arange(len(z["counts"]), dtype=np.float32))
+    return j, z
 
 
 SMALL = ["--steps", "1", "--warmup", "1", "--total-reads", "10", "--mem-conv", "8", "--rate", "3", "--msg-len", "164",
