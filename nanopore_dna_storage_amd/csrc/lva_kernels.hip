@@ -18,14 +18,16 @@
 //                    keeps all slots at the same step parity.  Equal scores on top, non-finite arithmetic and
 //                    fingerprint collisions queue the target for the exact path.
 //   lva_step_fixup_lazy   that exact path: one wavefront per queued target, the reference's heap merge (:743-800)
-//                    replayed literally on lane-resident values.
-//   lva_step_fast<L,P> + lva_step_fixup   the same tile with messages moved on every step (kernel mode 2 at L = 2/4/8).
+//                    replayed literally on lane-resident values (wave_merge), messages resolved through lazy_message.
+//   lva_step_fast<L,P>   the same tile with messages moved on every step (kernel mode 2 at L = 2/4/8).
 //   lva_step_acs<P>  L = 1: plain add-compare-select on the same tile, 256 threads.
-//   lva_step_big<LL,P> / lva_step_big_rec<LL> + lva_step_fixup_wave   other list sizes up to 64: list heads read on
-//                    demand; plane layout / record layout (Geometry::rec: records of 16, 24 or 32 bytes by trellis position).
-//   lva_step_wave    the literal merge with one wavefront per target over the whole step (kernel mode 3).
+//   lva_step_big<LL,P> / lva_step_big_rec<LL>   other list sizes up to 64: list heads read on demand; plane layout /
+//                    record layout (Geometry::rec: records of 16, 24 or 32 bytes by trellis position).
+//   lva_step_fixup_wave   the exact path behind lva_step_fast and the big-list kernels: wave_target (one wavefront per
+//                    queued target, wave_merge) over the work list.
+//   lva_step_wave    wave_target over the whole step (kernel mode 3).
 //   lva_step_exact   one thread per target state, the same literal merge straight from HBM -- any list size; kernel
-//                    mode 1, the default above 64 entries, and the overflow path of lva_step_fixup.
+//                    mode 1 and the default above 64 entries.
 //   lva_prepare_step per launch: slot descriptor -> this launch's SlotStep record of every slot
 //   lva_init_slot    initial scores (:657-663)
 //   lva_gather_final final state's lists -> result record (:806-815)
@@ -217,6 +219,10 @@ __device__ __forceinline__ uint32_t xcd_tile(uint32_t x, uint32_t xs) {
 __device__ __forceinline__ uint32_t make_item(uint32_t m, uint32_t z, uint32_t y, uint32_t k, uint32_t c) {
   return ((((z << 8) | y) << 3 | k) << m) | c;
 }
+struct Item { uint32_t z, y, k, c; };   // slot, band position index, crf state, conv state
+__device__ __forceinline__ Item read_item(uint32_t m, uint32_t it) {
+  return {it >> (m + 11), (it >> (m + 3)) & 0xFFu, (it >> m) & 7u, it & ((1u << m) - 1u)};
+}
 
 // ---- entry addressing: block base -> plane q of conv state c (2 words) ----
 __device__ __forceinline__ uint32_t plane_off(const Geometry& g, uint32_t q, uint32_t c) { return 2 * g.N * q + 2 * c; }
@@ -349,7 +355,9 @@ template <int W> __device__ __forceinline__ void push_var(uint32_t (&m)[W], uint
 }
 
 // ---------------------------------------------------------------------------------------
-// Exact merge of one target state by ONE thread, the reference's algorithm verbatim (:706-800).
+// Exact merge of one target state by ONE thread, the reference's algorithm verbatim (:706-800).  Serves lva_step_exact
+// (kernel mode 1) only: the thread-level restatement the wavefront paths (wave_merge) are checked against, so it shares no
+// merge code with them.
 // ---------------------------------------------------------------------------------------
 __device__ __noinline__ void exact_state(const Geometry& g, const SlotStep& ss, const uint32_t* __restrict__ prev,
                                          uint32_t* __restrict__ cur, const Target& tg, uint32_t pos) {
@@ -505,49 +513,37 @@ __global__ __launch_bounds__(256) void lva_step_exact(StepArgs args, Geometry g,
   if (resolve_target(cd, g, ss, pos, c, b + 4, &tg)) exact_state(g, ss, prev, cur, tg, pos);
 }
 
-// The exact merge of ONE target by ONE WAVEFRONT for list sizes 2..8 (the reference's heap merge :743-800 on
-// lane-resident values).  tg and pos are wavefront-uniform; all 64 lanes must be active.
-__device__ __forceinline__ void fixup_small(const Geometry& g, const SlotStep& ss, const uint32_t* __restrict__ prev,
-                                            uint32_t* __restrict__ cur, const Target& tg, uint32_t lane) {
-  const uint32_t L = g.L, sBlk = g.sBlk, sCrf = (uint32_t)g.sCrf, k = tg.k;
+namespace {
+
+// ---------------------------------------------------------------------------------------
+// The reference's k-way merge of ONE target by ONE WAVEFRONT (:743-800), list sizes 2 <= L <= 64: GCC 11
+// bits/stl_heap.h -- make_heap, then pop_heap with __adjust_heap and __push_heap -- and the fingerprint
+// de-duplication, restated on lane-resident values.  Everything the merge decides on is wavefront-uniform and lives in
+// registers spread over the lanes -- heap element e in lane e, accepted entry a in lane a -- read with v_readlane and
+// written with a lane select: a few cycles per access; the scan over the accepted fingerprints is ONE ballot instead
+// of a loop over L entries.  The caller holds the candidates, entry j of list i (i, j wavefront-uniform):
+//   score(i, j)     its score (-inf: no such entry; j < L),    fp(i, j)  its fingerprint with the step's delta applied
+//   word(i, j, w)   word w (per lane) of its message as it would stand in the target
+// addv: transition score of list i in lane i; Wd: message words in use at the target.  All 64 lanes must be active.
+// Returns the number l of accepted entries; entry a < l in lane a: score as, fingerprint ay, source ax = i << 16 | j.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ float lane_f(float v, uint32_t ln) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int)ln)); }
+__device__ __forceinline__ uint32_t lane_u(uint32_t v, uint32_t ln) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)ln); }
+
+template <typename ScoreF, typename FpF, typename WordF>
+__device__ __forceinline__ uint32_t wave_merge(uint32_t L, uint32_t nlists, uint32_t Wd, uint32_t lane, float addv, ScoreF score,
+                                               FpF fp, WordF word, float& as, uint32_t& ay, uint32_t& ax) {
   const float NEG = -INFINITY;
-  // Everything the merge decides on is wavefront-uniform and lives in registers spread over the
-  // lanes (candidate (list i, index j) in lane i*8+j, heap element e in lane e, accepted entry a
-  // in lane a), read with v_readlane and written with a lane-select: a few cycles per access.
-  auto rdf = [](float v, uint32_t ln) -> float { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int)ln)); };
-  auto rdu = [](uint32_t v, uint32_t ln) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)ln); };
   auto wrf = [lane](float& v, uint32_t ln, float x) { v = lane == ln ? x : v; };          // (clang 22 has no writelane builtin)
   auto wru = [lane](uint32_t& v, uint32_t ln, uint32_t x) { v = lane == ln ? x : v; };
-  // 1. candidates: lane = list*8 + index; transition score of list i in lane i
-  float cs = NEG; uint32_t cy = 0;
-  {
-    const uint32_t i = lane >> 3, j = lane & 7u;
-    if (i < tg.nlists && ((tg.okmask >> i) & 1u) && j < L) {
-      const uint32_t b = (i == 0 ? tg.own : tg.src + list_crf(k, i) * sCrf) + j * sBlk + 2 * (i == 0 ? tg.c : tg.cp);
-      const uint2 v = *reinterpret_cast<const uint2*>(prev + b);
-      cs = u2f(v.x); cy = i != 0 ? v.y ^ tg.fpc : v.y;
-    }
-  }
-  float addv = 0.0f;
-  if (lane < tg.nlists) addv = ss.post_row[tg.row * 8 + (lane == 0 ? k : list_crf(k, lane))];
-  // word w of the candidate message built from entry (li, lj) -- per lane, for full compares and output
-  auto word_of = [&](uint32_t li, uint32_t lj, uint32_t w) -> uint32_t {
-    const uint32_t b = (li == 0 ? tg.own : tg.src + list_crf(k, li) * sCrf) + lj * sBlk;
-    const uint32_t cv = li == 0 ? tg.c : tg.cp, np = li == 0 ? tg.np_dst : tg.np_src;
-    const uint32_t v = msg_word(g, prev, b, cv, w, np);
-    if (li == 0) return v;
-    const uint32_t lowpart = w == 0 ? tg.newbits : (msg_word(g, prev, b, cv, w - 1, np) >> (32 - tg.shift));
-    return (v << tg.shift) | lowpart;
-  };
-  // 2. the reference merge (:743-800): GCC 11 bits/stl_heap.h restated on lane-resident arrays
-  float hs = NEG; uint32_t hx = 0;                       // heap element e in lane e
-  float as = NEG; uint32_t ay = 0, ax = 0;               // accepted entry a in lane a: score, fingerprint, source
+  float hs = NEG; uint32_t hx = 0;                          // heap element e in lane e: score, (list << 16 | index in list)
+  as = NEG; ay = 0; ax = 0;
   auto sift_up = [&](uint32_t hole, uint32_t top, float vs, uint32_t vx) {
     while (hole > top) {
       const uint32_t parent = (hole - 1) / 2;
-      const float ps = rdf(hs, parent);
+      const float ps = lane_f(hs, parent);
       if (!(ps < vs)) break;
-      wrf(hs, hole, ps); wru(hx, hole, rdu(hx, parent));
+      wrf(hs, hole, ps); wru(hx, hole, lane_u(hx, parent));
       hole = parent;
     }
     wrf(hs, hole, vs); wru(hx, hole, vx);
@@ -557,75 +553,65 @@ __device__ __forceinline__ void fixup_small(const Geometry& g, const SlotStep& s
     uint32_t child = hole;
     while (child < (len - 1) / 2) {
       child = 2 * (child + 1);
-      if (rdf(hs, child) < rdf(hs, child - 1)) --child;
-      wrf(hs, hole, rdf(hs, child)); wru(hx, hole, rdu(hx, child));
+      if (lane_f(hs, child) < lane_f(hs, child - 1)) --child;
+      wrf(hs, hole, lane_f(hs, child)); wru(hx, hole, lane_u(hx, child));
       hole = child;
     }
     if ((len & 1u) == 0 && child == (len - 2) / 2) {
       child = 2 * (child + 1);
-      wrf(hs, hole, rdf(hs, child - 1)); wru(hx, hole, rdu(hx, child - 1));
+      wrf(hs, hole, lane_f(hs, child - 1)); wru(hx, hole, lane_u(hx, child - 1));
       hole = child - 1;
     }
     sift_up(hole, top, vs, vx);
   };
   uint32_t hn = 0;
-  for (uint32_t i = 0; i < tg.nlists; ++i) {                         // :750-761
-    const float head = rdf(cs, i * 8);
-    if (head != NEG) { wrf(hs, hn, head + rdf(addv, i)); wru(hx, hn, i << 16); ++hn; }
+  for (uint32_t i = 0; i < nlists; ++i) {                              // :750-761
+    const float head = score(i, 0);
+    if (head != NEG) { wrf(hs, hn, head + lane_f(addv, i)); wru(hx, hn, i << 16); ++hn; }
   }
-  if (hn >= 2)                                                       // std::make_heap :762
+  if (hn >= 2)                                                         // std::make_heap :762
     for (uint32_t parent = (hn - 2) / 2;; --parent) {
-      adjust(parent, hn, rdf(hs, parent), rdu(hx, parent));
+      adjust(parent, hn, lane_f(hs, parent), lane_u(hx, parent));
       if (parent == 0) break;
     }
   uint32_t l = 0;
-  const uint32_t Wd = 2 * tg.np_dst;
-  while (hn > 0 && l < L) {                                          // :764
-    const float ts = rdf(hs, 0); const uint32_t tx = rdu(hx, 0);     // pop_heap + back + pop_back :766-768
-    if (hn > 1) adjust(0, hn - 1, rdf(hs, hn - 1), rdu(hx, hn - 1));
+  while (hn > 0 && l < L) {                                            // :764
+    const float ts = lane_f(hs, 0); const uint32_t tx = lane_u(hx, 0); // pop_heap + back + pop_back :766-768
+    if (hn > 1) adjust(0, hn - 1, lane_f(hs, hn - 1), lane_u(hx, hn - 1));
     --hn;
     const uint32_t i = tx >> 16, j = tx & 0xFFFFu;
-    const uint32_t ch = rdu(cy, i * 8 + j);
-    bool dup = false;                                                // :778-779
-    unsigned long long match = __ballot(lane < l && ay == ch);      // different fingerprint => different message
+    const uint32_t ch = fp(i, j);
+    bool dup = false;                                                  // :778-779
+    unsigned long long match = __ballot(lane < l && ay == ch);        // different fingerprint => different message
     while (match && !dup) {
       const uint32_t a = (uint32_t)__builtin_ctzll(match);
       match &= match - 1;
-      const uint32_t asrc = rdu(ax, a);
-      uint32_t diff = 0;
-      if (lane < Wd) diff = word_of(i, j, lane) ^ word_of(asrc >> 16, asrc & 0xFFFFu, lane);
-      dup = __ballot(diff != 0) == 0ull;
+      const uint32_t asrc = lane_u(ax, a);
+      const uint32_t w = lane < Wd ? lane : 0u;                        // (every lane loads: no per-lane branch in front of word's loads)
+      const uint32_t diff = word(i, j, w) ^ word(asrc >> 16, asrc & 0xFFFFu, w);
+      dup = __ballot(lane < Wd && diff != 0) == 0ull;
     }
     if (!dup) { wrf(as, l, ts); wru(ay, l, ch); wru(ax, l, tx); ++l; }   // :780-783
-    if (j == L - 1) continue;                                        // :788
-    const float nxt = rdf(cs, i * 8 + j + 1);
-    if (nxt != NEG) {                                                // :790-796
-      sift_up(hn, 0, nxt + rdf(addv, i), (i << 16) | (j + 1));
+    if (j == L - 1) continue;                                          // :788
+    const float nxt = score(i, j + 1);
+    if (nxt != NEG) {                                                  // :790-796
+      sift_up(hn, 0, nxt + lane_f(addv, i), (i << 16) | (j + 1));
       ++hn;
     }
   }
-  // 3. outputs: lane = entry*8 + word
-  {
-    const uint32_t e = lane >> 3, w = lane & 7u;
-    const float es = __shfl(as, (int)e);
-    const uint32_t ey = __shfl(ay, (int)e), ex = __shfl(ax, (int)e);
-    if (e < L && w == 0)
-      *reinterpret_cast<uint2*>(cur + tg.own + e * sBlk + 2 * tg.c) = e < l ? make_uint2(f2u(es), ey) : make_uint2(kNegInfBits, 0u);
-    if (e < l && w < Wd)
-      cur[tg.own + e * sBlk + 2 * g.N + msg_word_off(g.N, tg.c, w, tg.np_dst)] = word_of(ex >> 16, ex & 0xFFFFu, w);
-  }
+  return l;
 }
 
-// ---------------------------------------------------------------------------------------
-// fix-up kernel: exact path over the fast kernel's work list, ONE WAVEFRONT PER TARGET.
-// item: make_item().   Requires 2 <= L <= 8.
-// All 64 lanes run the same (uniform) merge on register-resident candidate heads (one per lane,
-// v_readlane access); loads and stores of the 8x8 candidate entries are spread over the lanes, so
-// one target costs a few memory round trips instead of a few hundred.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void lva_step_fixup(StepArgs args, Geometry g, const DevCode* __restrict__ codes,
+// The targets of one fix-up launch, one wavefront per target (workgroups of 256 threads): the work list the fast kernel
+// filled (make_item), or -- when it overflowed (tie-dense posteriors: quantised or constant matrices) -- the whole step once
+// more, every target of every active slot, whatever the fast kernel wrote for it (the exact path reads only the previous
+// step's rows and message rows no step is writing, so redoing a target is idempotent).  The overflow pass stays on the
+// wavefront path: a call of the thread-per-target exact_state would cost a fix-up kernel 114 registers and its candidate
+// registers a place in scratch memory.  fn(cd, ss, prev, cur, tg, pos) gets wavefront-uniform values only.
+template <typename Fn>
+__device__ __forceinline__ void for_each_fixup_target(const StepArgs& args, const Geometry& g, const DevCode* __restrict__ codes,
                                                       uint32_t* __restrict__ trellis, WorkHdr* __restrict__ hdr,
-                                                      const uint32_t* __restrict__ items) {
+                                                      const uint32_t* __restrict__ items, Fn fn) {
   const uint32_t par = args.step_parity;
   const uint32_t n = hdr->count[par] < hdr->cap ? hdr->count[par] : hdr->cap;
   const bool all = hdr->overflow[par] != 0;
@@ -633,48 +619,30 @@ __global__ __launch_bounds__(256) void lva_step_fixup(StepArgs args, Geometry g,
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     if (all) atomicAdd(&hdr->overflow_steps, 1u); else atomicAdd(&hdr->total, (unsigned long long)n);
   }
+  const uint32_t wv = threadIdx.x >> 6, nwaves = gridDim.x * 4;
+  const uint32_t mm = codes[0].m;
+  const uint32_t nouter = all ? args.nslots : 1u, ninner = all ? (args.band_max << (mm + 3)) : n;   // (N = 2^m conv states, 8 crf states)
   Target tg;
-  if (all) {   // work list overflowed: redo the whole step, one thread per target
-    const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
-    const uint64_t per_slot = (uint64_t)args.band_max * g.N * 8, total = per_slot * args.nslots;
-    for (uint64_t idx = gid; idx < total; idx += stride) {
-      const uint32_t si = (uint32_t)(idx / per_slot);
-      const uint32_t rem = (uint32_t)(idx % per_slot);
-      SlotStep ss;
-      if (!load_slot(args, si, &ss)) continue;
-      const uint32_t c = rem % g.N, k = (rem / g.N) & 7u, pos = ss.lo + rem / (g.N * 8);
-      if (pos >= ss.hi) continue;
-      const uint32_t* prev; uint32_t* cur;
-      slot_buffers(ss, g, trellis, &prev, &cur);
-      if (resolve_target(codes[ss.orient], g, ss, pos, c, k, &tg)) exact_state(g, ss, prev, cur, tg, pos);
-    }
-    return;
-  }
-
-  const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  const uint32_t nwaves = gridDim.x * 4;
-  for (uint32_t idx = blockIdx.x * 4 + wv; idx < n; idx += nwaves) {
-    const uint32_t it = items[idx];
-    const uint32_t mm = codes[0].m;
+  for (uint32_t si = 0; si < nouter; ++si)
+  for (uint32_t idx = blockIdx.x * 4 + wv; idx < ninner; idx += nwaves) {
+    const Item it = read_item(mm, all ? ((si << (mm + 11)) | idx) : items[idx]);   // (uniform per wavefront)
     SlotStep ss;
-    if (!load_slot(args, it >> (mm + 11), &ss)) continue;
-    const uint32_t pos = ss.lo + ((it >> (mm + 3)) & 0xFFu), k = (it >> mm) & 7u, c = it & ((1u << mm) - 1u);
+    if (!load_slot(args, it.z, &ss)) continue;
+    const uint32_t pos = ss.lo + it.y;
+    if (pos >= ss.hi) continue;            // (whole-step pass: band positions beyond this slot's band)
+    const DevCode& cd = codes[ss.orient];
     const uint32_t* prev; uint32_t* cur;
     slot_buffers(ss, g, trellis, &prev, &cur);
-    if (!resolve_target(codes[ss.orient], g, ss, pos, c, k, &tg)) continue;   // (uniform per wavefront)
-    if (pos == 0) continue;              // position 0 never reaches the work list
-    fixup_small(g, ss, prev, cur, tg, lane);
+    if (!resolve_target(cd, g, ss, pos, it.c, it.k, &tg)) continue;   // (uniform per wavefront)
+    fn(cd, ss, prev, cur, tg, pos);
   }
 }
 
 // ---------------------------------------------------------------------------------------
-// The literal reference merge of ONE target by ONE WAVEFRONT, list sizes 2 <= L <= 64.  Lane j
-// holds entry j of each of the target's <= 8 candidate lists (8 registers), heap element e lives
-// in lane e, accepted entry a in lane a; the merge itself is wavefront-uniform (v_readlane), the
-// de-duplication scan over the accepted fingerprints is ONE ballot instead of a loop over L
-// entries, and all loads/stores of list entries are spread over the lanes.
+// The literal reference merge of ONE target by ONE WAVEFRONT (wave_merge), list sizes 2 <= L <= 64, either layout.
+// Lane j holds entry j of each of the target's <= 8 candidate lists (8 registers); all loads/stores of list entries
+// are spread over the lanes.
 // ---------------------------------------------------------------------------------------
-namespace {
 __device__ __forceinline__ void wave_target(const Geometry& g, const SlotStep& ss, const uint32_t* __restrict__ prev,
                                             uint32_t* __restrict__ cur, const Target& tg, uint32_t pos, uint32_t lane) {
   const uint32_t k = tg.k;
@@ -691,10 +659,6 @@ __device__ __forceinline__ void wave_target(const Geometry& g, const SlotStep& s
     if (lane >= 1 && lane < L) cur[rec_sh(g, tg.own, tg.c, lane, tg.np_dst)] = kNegInfBits;
     return;
   }
-  auto rdf = [](float v, uint32_t ln) -> float { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int)ln)); };
-  auto rdu = [](uint32_t v, uint32_t ln) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)ln); };
-  auto wrf = [lane](float& v, uint32_t ln, float x) { v = lane == ln ? x : v; };
-  auto wru = [lane](uint32_t& v, uint32_t ln, uint32_t x) { v = lane == ln ? x : v; };
   // 1. candidates: register i of lane j = entry j of list i (score, fingerprint with the step's delta applied)
   float cs[8]; uint32_t cy[8];
 #pragma unroll
@@ -710,13 +674,13 @@ __device__ __forceinline__ void wave_target(const Geometry& g, const SlotStep& s
     float v = opq(cs[0]);                                   // (opaque copies: a plain select chain is folded into an indexed
 #pragma unroll                                              //  load and the array then lives in scratch memory)
     for (uint32_t u = 1; u < 8; ++u) v = i == u ? opq(cs[u]) : v;
-    return rdf(v, j);
+    return lane_f(v, j);
   };
   auto cand_y = [&](uint32_t i, uint32_t j) -> uint32_t {
     uint32_t v = opq(cy[0]);
 #pragma unroll
     for (uint32_t u = 1; u < 8; ++u) v = i == u ? opq(cy[u]) : v;
-    return rdu(v, j);
+    return lane_u(v, j);
   };
   float addv = 0.0f;                                        // transition score of list i in lane i
   if (lane < tg.nlists) addv = ss.post_row[tg.row * 8 + (lane == 0 ? k : list_crf(k, lane))];
@@ -729,70 +693,9 @@ __device__ __forceinline__ void wave_target(const Geometry& g, const SlotStep& s
     const uint32_t lowpart = w == 0 ? tg.newbits : (entry_word(g, prev, lst, cv, lj, w - 1, np) >> (32 - tg.shift));
     return (v << tg.shift) | lowpart;
   };
-  // 2. the reference merge (:743-800): GCC 11 bits/stl_heap.h restated on lane-resident arrays
-  float hs = NEG; uint32_t hx = 0;                          // heap element e in lane e
-  float as = NEG; uint32_t ay = 0, ax = 0;                  // accepted entry a in lane a
-  auto sift_up = [&](uint32_t hole, uint32_t top, float vs, uint32_t vx) {
-    while (hole > top) {
-      const uint32_t parent = (hole - 1) / 2;
-      const float ps = rdf(hs, parent);
-      if (!(ps < vs)) break;
-      wrf(hs, hole, ps); wru(hx, hole, rdu(hx, parent));
-      hole = parent;
-    }
-    wrf(hs, hole, vs); wru(hx, hole, vx);
-  };
-  auto adjust = [&](uint32_t hole, uint32_t len, float vs, uint32_t vx) {
-    const uint32_t top = hole;
-    uint32_t child = hole;
-    while (child < (len - 1) / 2) {
-      child = 2 * (child + 1);
-      if (rdf(hs, child) < rdf(hs, child - 1)) --child;
-      wrf(hs, hole, rdf(hs, child)); wru(hx, hole, rdu(hx, child));
-      hole = child;
-    }
-    if ((len & 1u) == 0 && child == (len - 2) / 2) {
-      child = 2 * (child + 1);
-      wrf(hs, hole, rdf(hs, child - 1)); wru(hx, hole, rdu(hx, child - 1));
-      hole = child - 1;
-    }
-    sift_up(hole, top, vs, vx);
-  };
-  uint32_t hn = 0;
-  for (uint32_t i = 0; i < tg.nlists; ++i) {                           // :750-761
-    const float head = cand_s(i, 0);
-    if (head != NEG) { wrf(hs, hn, head + rdf(addv, i)); wru(hx, hn, i << 16); ++hn; }
-  }
-  if (hn >= 2)                                                         // std::make_heap :762
-    for (uint32_t parent = (hn - 2) / 2;; --parent) {
-      adjust(parent, hn, rdf(hs, parent), rdu(hx, parent));
-      if (parent == 0) break;
-    }
-  uint32_t l = 0;
-  while (hn > 0 && l < L) {                                            // :764
-    const float ts = rdf(hs, 0); const uint32_t tx = rdu(hx, 0);       // pop_heap + back + pop_back :766-768
-    if (hn > 1) adjust(0, hn - 1, rdf(hs, hn - 1), rdu(hx, hn - 1));
-    --hn;
-    const uint32_t i = tx >> 16, j = tx & 0xFFFFu;
-    const uint32_t ch = cand_y(i, j);
-    bool dup = false;                                                  // :778-779
-    unsigned long long match = __ballot(lane < l && ay == ch);        // different fingerprint => different message
-    while (match && !dup) {
-      const uint32_t a = (uint32_t)__builtin_ctzll(match);
-      match &= match - 1;
-      const uint32_t asrc = rdu(ax, a);
-      uint32_t diff = 0;
-      if (lane < Wd) diff = word_of(i, j, lane) ^ word_of(asrc >> 16, asrc & 0xFFFFu, lane);
-      dup = __ballot(diff != 0) == 0ull;
-    }
-    if (!dup) { wrf(as, l, ts); wru(ay, l, ch); wru(ax, l, tx); ++l; }   // :780-783
-    if (j == L - 1) continue;                                          // :788
-    const float nxt = cand_s(i, j + 1);
-    if (nxt != NEG) {                                                  // :790-796
-      sift_up(hn, 0, nxt + rdf(addv, i), (i << 16) | (j + 1));
-      ++hn;
-    }
-  }
+  // 2. the reference merge (:743-800)
+  float as; uint32_t ay, ax;
+  const uint32_t l = wave_merge(L, tg.nlists, Wd, lane, addv, cand_s, cand_y, word_of, as, ay, ax);
   // 3. outputs: lane a writes list entry a (:781, :799) and, if accepted, its message
   if (lane < L) {
     *reinterpret_cast<uint2*>(cur + rec_sh(g, tg.own, tg.c, lane, tg.np_dst)) = lane < l ? make_uint2(f2u(as), ay) : make_uint2(kNegInfBits, 0u);
@@ -842,36 +745,16 @@ __global__ __launch_bounds__(256) void lva_step_wave(StepArgs args, Geometry g, 
   wave_target(g, ss, prev, cur, tg, pos, threadIdx.x & 63u);
 }
 
-// fix-up pass behind the big-list fast kernel (8 < L <= 64, and list sizes that are not a power of
-// two): wave_target over the work list; same item format and overflow behaviour as lva_step_fixup.
+// fix-up pass behind lva_step_fast (L = 2/4/8) and the big-list fast kernels (8 < L <= 64, and list sizes that are not a
+// power of two): wave_target over the work list (position 0, reached only by the whole-step pass, is idempotent there).
 __global__ __launch_bounds__(256, 8) void lva_step_fixup_wave(StepArgs args, Geometry g, const DevCode* __restrict__ codes,
                                                            uint32_t* __restrict__ trellis, WorkHdr* __restrict__ hdr,
                                                            const uint32_t* __restrict__ items) {
-  const uint32_t par = args.step_parity;
-  const uint32_t n = hdr->count[par] < hdr->cap ? hdr->count[par] : hdr->cap;
-  const bool all = hdr->overflow[par] != 0;
-  if (n == 0 && !all) return;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (all) atomicAdd(&hdr->overflow_steps, 1u); else atomicAdd(&hdr->total, (unsigned long long)n);
-  }
-  // work list overflowed: the whole step once more on this exact path (every target of every slot; no other code in this
-  // kernel -- a call of the thread-per-target routine would cost it 114 registers and its candidate registers a place in scratch memory)
-  const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u, nwaves = gridDim.x * 4;
-  const uint32_t mm = codes[0].m;
-  const uint32_t nouter = all ? args.nslots : 1u, ninner = all ? (args.band_max << (mm + 3)) : n;   // (N = 2^m conv states, 8 crf states)
-  Target tg;
-  for (uint32_t si = 0; si < nouter; ++si)
-  for (uint32_t idx = blockIdx.x * 4 + wv; idx < ninner; idx += nwaves) {
-    const uint32_t it = all ? ((si << (mm + 11)) | idx) : items[idx];      // (uniform per wavefront; make_item's format)
-    SlotStep ss;
-    if (!load_slot(args, it >> (mm + 11), &ss)) continue;
-    const uint32_t pos = ss.lo + ((it >> (mm + 3)) & 0xFFu), k = (it >> mm) & 7u, c = it & ((1u << mm) - 1u);
-    if (pos >= ss.hi) continue;            // (whole-step pass: band positions beyond this slot's band)
-    const uint32_t* prev; uint32_t* cur;
-    slot_buffers(ss, g, trellis, &prev, &cur);
-    if (!resolve_target(codes[ss.orient], g, ss, pos, c, k, &tg)) continue;   // (uniform per wavefront)
-    wave_target(g, ss, prev, cur, tg, pos, lane);
-  }
+  const uint32_t lane = threadIdx.x & 63u;
+  for_each_fixup_target(args, g, codes, trellis, hdr, items,
+                        [&](const DevCode&, const SlotStep& ss, const uint32_t* prev, uint32_t* cur, const Target& tg, uint32_t pos) {
+                          wave_target(g, ss, prev, cur, tg, pos, lane);
+                        });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1673,56 +1556,24 @@ __global__ __launch_bounds__(8 * TS, kLazyMinWaves) void lva_step_lazy(StepArgs 
 }
 
 // exact path behind lva_step_lazy: one wavefront per queued target, the reference merge (:743-800) on lane-resident values
-// as fixup_small, messages resolved through lazy_message.
+// (wave_merge), messages resolved through lazy_message.
 template <int P>
 __global__ __launch_bounds__(256) void lva_step_fixup_lazy(StepArgs args, Geometry g, const DevCode* __restrict__ codes,
                                                            uint32_t* __restrict__ trellis, WorkHdr* __restrict__ hdr,
                                                            const uint32_t* __restrict__ items) {
-  const uint32_t par = args.step_parity;
-  const uint32_t n = hdr->count[par] < hdr->cap ? hdr->count[par] : hdr->cap;
-  // work list overflowed (tie-dense posteriors: quantised or constant matrices): the whole step is redone on the exact path,
-  // still one wavefront per target -- every target of every active slot, whatever the fast kernel wrote for it (the
-  // exact path reads only the previous step's rows and message rows no step is writing, so redoing a target is idempotent)
-  const bool all = hdr->overflow[par] != 0;
-  if (n == 0 && !all) return;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (all) atomicAdd(&hdr->overflow_steps, 1u); else atomicAdd(&hdr->total, (unsigned long long)n);
-  }
-  const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u, nwaves = gridDim.x * 4;
-  const uint32_t mm = codes[0].m;
-  const uint64_t per_slot = (uint64_t)args.band_max * g.N * 8;
-  const uint64_t ntargets = all ? per_slot * args.nslots : (uint64_t)n;
+  const uint32_t lane = threadIdx.x & 63u;
   const uint32_t L = g.L, sBlk = g.sBlk, sCrf = (uint32_t)g.sCrf;
-  const float NEG = -INFINITY;
-  auto rdf = [](float v, uint32_t ln) -> float { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int)ln)); };
-  auto rdu = [](uint32_t v, uint32_t ln) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)ln); };
-  auto wrf = [lane](float& v, uint32_t ln, float x) { v = lane == ln ? x : v; };
-  auto wru = [lane](uint32_t& v, uint32_t ln, uint32_t x) { v = lane == ln ? x : v; };
-  for (uint64_t idx = blockIdx.x * 4 + wv; idx < ntargets; idx += nwaves) {
-    uint32_t it;                           // (uniform per wavefront)
-    if (all) {
-      const uint32_t si = (uint32_t)(idx / per_slot), rem = (uint32_t)(idx % per_slot);
-      it = make_item(mm, si, rem / (g.N * 8), (rem / g.N) & 7u, rem % g.N);
-    } else {
-      it = items[idx];
-    }
-    SlotStep ss;
-    if (!load_slot(args, it >> (mm + 11), &ss)) continue;
-    const uint32_t pos = ss.lo + ((it >> (mm + 3)) & 0xFFu), k = (it >> mm) & 7u, c = it & ((1u << mm) - 1u);
-    if (pos >= ss.hi) continue;            // (whole-step pass: band positions beyond this slot's band)
-    const DevCode& cd = codes[ss.orient];
-    const uint32_t* prev; uint32_t* cur;
-    slot_buffers(ss, g, trellis, &prev, &cur);
+  for_each_fixup_target(args, g, codes, trellis, hdr, items,
+                        [&](const DevCode& cd, const SlotStep& ss, const uint32_t* prev, uint32_t* cur, const Target& tg, uint32_t pos) {
+    if (pos == 0) return;                  // the fast kernel's stay-only update of position 0 is exact
+    const uint32_t k = tg.k;
     uint32_t* slot_base = trellis + (uint64_t)ss.slot * g.sSlot;
     uint32_t* mout = slot_base + (uint64_t)((ss.t >> 1) & 1u) * g.sPar;
-    Target tg;
-    if (!resolve_target(cd, g, ss, pos, c, k, &tg)) continue;   // (uniform per wavefront)
-    if (pos == 0) continue;                // the fast kernel's stay-only update of position 0 is exact
     LazyCtx x;
     lazy_ctx(cd, g, ss, slot_base, pos, tg.c, tg.cp, k, tg.own, &x);
     const bool anchor = !(ss.t & 1u);
     // 1. candidates: lane = list*8 + index
-    float cs = NEG; uint32_t cy = 0, cb = 0;
+    float cs = -INFINITY; uint32_t cy = 0, cb = 0;
     {
       const uint32_t i = lane >> 3, j = lane & 7u;
       if (i < tg.nlists && ((tg.okmask >> i) & 1u) && j < L) {
@@ -1737,77 +1588,17 @@ __global__ __launch_bounds__(256) void lva_step_fixup_lazy(StepArgs args, Geomet
     // word w of the candidate message of entry (li, lj): every lane computes the whole message and picks its word
     auto word_of = [&](uint32_t li, uint32_t lj, uint32_t w) -> uint32_t {
       uint32_t mw[2 * P];
-      lazy_message<P>(x, li, lj, rdu(cb, li * 8 + lj), mw);
+      lazy_message<P>(x, li, lj, lane_u(cb, li * 8 + lj), mw);
       uint32_t v = 0;
 #pragma unroll
       for (int u = 0; u < 2 * P; ++u) v = w == (uint32_t)u ? mw[u] : v;
       return v;
     };
-    float hs = NEG; uint32_t hx = 0;
-    float as = NEG; uint32_t ay = 0, ax = 0;
-    auto sift_up = [&](uint32_t hole, uint32_t top, float vs, uint32_t vx) {
-      while (hole > top) {
-        const uint32_t parent = (hole - 1) / 2;
-        const float ps = rdf(hs, parent);
-        if (!(ps < vs)) break;
-        wrf(hs, hole, ps); wru(hx, hole, rdu(hx, parent));
-        hole = parent;
-      }
-      wrf(hs, hole, vs); wru(hx, hole, vx);
-    };
-    auto adjust = [&](uint32_t hole, uint32_t len, float vs, uint32_t vx) {
-      const uint32_t top = hole;
-      uint32_t child = hole;
-      while (child < (len - 1) / 2) {
-        child = 2 * (child + 1);
-        if (rdf(hs, child) < rdf(hs, child - 1)) --child;
-        wrf(hs, hole, rdf(hs, child)); wru(hx, hole, rdu(hx, child));
-        hole = child;
-      }
-      if ((len & 1u) == 0 && child == (len - 2) / 2) {
-        child = 2 * (child + 1);
-        wrf(hs, hole, rdf(hs, child - 1)); wru(hx, hole, rdu(hx, child - 1));
-        hole = child - 1;
-      }
-      sift_up(hole, top, vs, vx);
-    };
-    uint32_t hn = 0;
-    for (uint32_t i = 0; i < tg.nlists; ++i) {                         // :750-761
-      const float head = rdf(cs, i * 8);
-      if (head != NEG) { wrf(hs, hn, head + rdf(addv, i)); wru(hx, hn, i << 16); ++hn; }
-    }
-    if (hn >= 2)                                                       // std::make_heap :762
-      for (uint32_t parent = (hn - 2) / 2;; --parent) {
-        adjust(parent, hn, rdf(hs, parent), rdu(hx, parent));
-        if (parent == 0) break;
-      }
-    uint32_t l = 0;
+    // 2. the reference merge (:743-800)
     const uint32_t Wd = 2 * tg.np_dst;
-    while (hn > 0 && l < L) {                                          // :764
-      const float ts = rdf(hs, 0); const uint32_t tx = rdu(hx, 0);
-      if (hn > 1) adjust(0, hn - 1, rdf(hs, hn - 1), rdu(hx, hn - 1));
-      --hn;
-      const uint32_t i = tx >> 16, j = tx & 0xFFFFu;
-      const uint32_t ch = rdu(cy, i * 8 + j);
-      bool dup = false;                                                // :778-779
-      unsigned long long match = __ballot(lane < l && ay == ch);
-      while (match && !dup) {
-        const uint32_t a = (uint32_t)__builtin_ctzll(match);
-        match &= match - 1;
-        const uint32_t asrc = rdu(ax, a);
-        uint32_t diff = 0;
-        const uint32_t wa = word_of(i, j, lane < Wd ? lane : 0u), wb2 = word_of(asrc >> 16, asrc & 0xFFFFu, lane < Wd ? lane : 0u);
-        if (lane < Wd) diff = wa ^ wb2;
-        dup = __ballot(diff != 0) == 0ull;
-      }
-      if (!dup) { wrf(as, l, ts); wru(ay, l, ch); wru(ax, l, tx); ++l; }
-      if (j == L - 1) continue;
-      const float nxt = rdf(cs, i * 8 + j + 1);
-      if (nxt != NEG) {
-        sift_up(hn, 0, nxt + rdf(addv, i), (i << 16) | (j + 1));
-        ++hn;
-      }
-    }
+    float as; uint32_t ay, ax;
+    const uint32_t l = wave_merge(L, tg.nlists, Wd, lane, addv, [&](uint32_t i, uint32_t j) { return lane_f(cs, i * 8 + j); },
+                                  [&](uint32_t i, uint32_t j) { return lane_u(cy, i * 8 + j); }, word_of, as, ay, ax);
     // 3. outputs: lane = entry*8 + word
     {
       const uint32_t e = lane >> 3, w = lane & 7u;
@@ -1830,7 +1621,7 @@ __global__ __launch_bounds__(256) void lva_step_fixup_lazy(StepArgs args, Geomet
         reinterpret_cast<uint8_t*>(cur)[bp_byte_index(g, tg.own, e, tg.c)] = (uint8_t)((li << 3) | lj | (lazy_mbuf(x, li) << 6));
       }
     }
-  }
+  });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2595,107 +2386,71 @@ bool fast_kernel_available(const Geometry& g) {
   return l_ok && g.P >= 1 && g.P <= 4 && g.N >= 64;
 }
 
-template <int LL>
-static int launch_fast_p(const StepArgs& a, const Geometry& g, const DevCode* codes, uint32_t* trellis, WorkHdr* hdr,
-                         uint32_t* items, hipStream_t st) {
-  dim3 grid(g.N / TS, a.band_max, a.nslots), block(8 * TS);
-  switch (g.P) {
-    case 1: hipLaunchKernelGGL((lva_step_fast<LL, 1>), grid, block, 0, st, a, g, codes, trellis, hdr, items); break;
-    case 2: hipLaunchKernelGGL((lva_step_fast<LL, 2>), grid, block, 0, st, a, g, codes, trellis, hdr, items); break;
-    case 3: hipLaunchKernelGGL((lva_step_fast<LL, 3>), grid, block, 0, st, a, g, codes, trellis, hdr, items); break;
-    case 4: hipLaunchKernelGGL((lva_step_fast<LL, 4>), grid, block, 0, st, a, g, codes, trellis, hdr, items); break;
-    default: return (int)hipErrorInvalidValue;
-  }
-  return (int)hipGetLastError();
-}
-
-template <int LL>
-static int launch_big_p(const StepArgs& a, const Geometry& g, const DevCode* codes, uint32_t* trellis, WorkHdr* hdr,
-                        uint32_t* items, hipStream_t st) {
-  dim3 grid(g.N / TSB, a.band_max, a.nslots), block(8 * TSB);
-  switch (g.P) {
-    case 1: hipLaunchKernelGGL((lva_step_big<LL, 1>), grid, block, 0, st, a, g, codes, trellis, hdr, items); break;
-    case 2: hipLaunchKernelGGL((lva_step_big<LL, 2>), grid, block, 0, st, a, g, codes, trellis, hdr, items); break;
-    case 3: hipLaunchKernelGGL((lva_step_big<LL, 3>), grid, block, 0, st, a, g, codes, trellis, hdr, items); break;
-    case 4: hipLaunchKernelGGL((lva_step_big<LL, 4>), grid, block, 0, st, a, g, codes, trellis, hdr, items); break;
-    default: return (int)hipErrorInvalidValue;
-  }
-  return (int)hipGetLastError();
+// f(std::integral_constant<int, V>{}) for the V of Vs that equals the run-time value v (a list size, a message plane count):
+// f's result, or hipErrorInvalidValue when v is none of them
+template <int... Vs, typename F>
+static int with_constant(uint32_t v, F&& f) {
+  int e = (int)hipErrorInvalidValue;
+  ((v == (uint32_t)Vs ? (void)(e = f(std::integral_constant<int, Vs>{})) : (void)0), ...);
+  return e;
 }
 
 int launch_step_fast(const StepArgs& a, const Geometry& g, const DevCode* codes, uint32_t* trellis, WorkHdr* hdr,
                      uint32_t* items, void* stream, void* ev_mid) {
   if (a.nslots == 0 || a.band_max == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(g.N / TS, a.band_max, a.nslots), grid_big(g.N / TSB, a.band_max, a.nslots);
+  // 1. the dominant kernel
   int e;
-  if (!small_list(g)) {   // big-list kernel + wavefront-per-target fix-up
-    if (g.rec) {          // record layout (three message planes, 32 <= L <= 64, L a multiple of 4)
-      dim3 grid(g.N / TSB, a.band_max, a.nslots), block(8 * TSB);
-      if (g.L <= 32) hipLaunchKernelGGL((lva_step_big_rec<32>), grid, block, 0, st, a, g, codes, trellis, hdr, items);
-      else hipLaunchKernelGGL((lva_step_big_rec<64>), grid, block, 0, st, a, g, codes, trellis, hdr, items);
-      e = (int)hipGetLastError();
-    } else
-    e = g.L <= 16 ? launch_big_p<16>(a, g, codes, trellis, hdr, items, st)
-      : g.L <= 32 ? launch_big_p<32>(a, g, codes, trellis, hdr, items, st)
-                  : launch_big_p<64>(a, g, codes, trellis, hdr, items, st);
-    if (e) return e;
-    if (ev_mid && (e = (int)hipEventRecord((hipEvent_t)ev_mid, st))) return e;
-    hipLaunchKernelGGL(lva_step_fixup_wave, dim3(4096), dim3(256), 0, st, a, g, codes, trellis, hdr, items);
-    return (int)hipGetLastError();
-  }
-  if (g.lazy) {
-    dim3 grid(g.N / TS, a.band_max, a.nslots), block(8 * TS);
+  if (!small_list(g) && g.rec) {   // big-list kernel, record layout (three message planes, 32 <= L <= 64, L a multiple of 4)
+    if (g.L <= 32) hipLaunchKernelGGL((lva_step_big_rec<32>), grid_big, dim3(8 * TSB), 0, st, a, g, codes, trellis, hdr, items);
+    else hipLaunchKernelGGL((lva_step_big_rec<64>), grid_big, dim3(8 * TSB), 0, st, a, g, codes, trellis, hdr, items);
+    e = (int)hipGetLastError();
+  } else if (!small_list(g)) {     // big-list kernel, plane layout
+    e = with_constant<1, 2, 3, 4>(g.P, [&](auto p) {
+      constexpr int P = decltype(p)::value;
+      if (g.L <= 16) hipLaunchKernelGGL((lva_step_big<16, P>), grid_big, dim3(8 * TSB), 0, st, a, g, codes, trellis, hdr, items);
+      else if (g.L <= 32) hipLaunchKernelGGL((lva_step_big<32, P>), grid_big, dim3(8 * TSB), 0, st, a, g, codes, trellis, hdr, items);
+      else hipLaunchKernelGGL((lva_step_big<64, P>), grid_big, dim3(8 * TSB), 0, st, a, g, codes, trellis, hdr, items);
+      return (int)hipGetLastError();
+    });
+  } else if (g.lazy) {
     // phase-aligned slots (the host starts every read on an even launch): all slots are at an even time step on even launches
     // and at an odd one on odd launches -- one instance per launch, no workgroups of the wrong kind
     const bool run_anchor = !a.phase_aligned || !(a.launch_no & 1u), run_odd = !a.phase_aligned || (a.launch_no & 1u);
-#define LVA_LAZY_CASE(LLv, Pv) { if (run_anchor) hipLaunchKernelGGL((lva_step_lazy<LLv, Pv, true>), grid, block, 0, st, a, g, codes, trellis, hdr, items); \
-                                 if (run_odd) hipLaunchKernelGGL((lva_step_lazy<LLv, Pv, false>), grid, block, 0, st, a, g, codes, trellis, hdr, items); }
-#define LVA_LAZY_L(LLv) switch (g.P) { case 1: LVA_LAZY_CASE(LLv, 1); break; case 2: LVA_LAZY_CASE(LLv, 2); break; \
-                                      case 3: LVA_LAZY_CASE(LLv, 3); break; case 4: LVA_LAZY_CASE(LLv, 4); break; default: return (int)hipErrorInvalidValue; }
-    switch (g.L) {
-      case 2: LVA_LAZY_L(2); break;
-      case 4: LVA_LAZY_L(4); break;
-      case 8: LVA_LAZY_L(8); break;
-      default: return (int)hipErrorInvalidValue;
-    }
-    e = (int)hipGetLastError();
-    if (e) return e;
-    if (ev_mid && (e = (int)hipEventRecord((hipEvent_t)ev_mid, st))) return e;
-    // one target per wavefront and pass: the pass is a chain of dependent round trips, so more (mostly idle) wavefronts, not fewer
-    constexpr uint32_t kFixGrid = kFixupLazyGrid;
-    switch (g.P) {
-      case 1: hipLaunchKernelGGL((lva_step_fixup_lazy<1>), dim3(kFixGrid), dim3(256), 0, st, a, g, codes, trellis, hdr, items); break;
-      case 2: hipLaunchKernelGGL((lva_step_fixup_lazy<2>), dim3(kFixGrid), dim3(256), 0, st, a, g, codes, trellis, hdr, items); break;
-      case 3: hipLaunchKernelGGL((lva_step_fixup_lazy<3>), dim3(kFixGrid), dim3(256), 0, st, a, g, codes, trellis, hdr, items); break;
-      default: hipLaunchKernelGGL((lva_step_fixup_lazy<4>), dim3(kFixGrid), dim3(256), 0, st, a, g, codes, trellis, hdr, items); break;
-    }
-    return (int)hipGetLastError();
-  }
-  switch (g.L) {
-    case 1: {
-      dim3 grid(g.N / TS, a.band_max, a.nslots), block(4 * TS);
-      switch (g.P) {
-        case 1: hipLaunchKernelGGL((lva_step_acs<1>), grid, block, 0, st, a, g, codes, trellis); break;
-        case 2: hipLaunchKernelGGL((lva_step_acs<2>), grid, block, 0, st, a, g, codes, trellis); break;
-        case 3: hipLaunchKernelGGL((lva_step_acs<3>), grid, block, 0, st, a, g, codes, trellis); break;
-        case 4: hipLaunchKernelGGL((lva_step_acs<4>), grid, block, 0, st, a, g, codes, trellis); break;
-        default: return (int)hipErrorInvalidValue;
-      }
-      e = (int)hipGetLastError();
-      break;
-    }
-    case 2: e = launch_fast_p<2>(a, g, codes, trellis, hdr, items, st); break;
-    case 4: e = launch_fast_p<4>(a, g, codes, trellis, hdr, items, st); break;
-    case 8: e = launch_fast_p<8>(a, g, codes, trellis, hdr, items, st); break;
-    default: return (int)hipErrorInvalidValue;
+    e = with_constant<2, 4, 8>(g.L, [&](auto ll) {
+      return with_constant<1, 2, 3, 4>(g.P, [&](auto p) {
+        constexpr int LL = decltype(ll)::value, P = decltype(p)::value;
+        if (run_anchor) hipLaunchKernelGGL((lva_step_lazy<LL, P, true>), grid, dim3(8 * TS), 0, st, a, g, codes, trellis, hdr, items);
+        if (run_odd) hipLaunchKernelGGL((lva_step_lazy<LL, P, false>), grid, dim3(8 * TS), 0, st, a, g, codes, trellis, hdr, items);
+        return (int)hipGetLastError();
+      });
+    });
+  } else if (g.L == 1) {
+    e = with_constant<1, 2, 3, 4>(g.P, [&](auto p) {
+      hipLaunchKernelGGL((lva_step_acs<decltype(p)::value>), grid, dim3(4 * TS), 0, st, a, g, codes, trellis);
+      return (int)hipGetLastError();
+    });
+  } else {
+    e = with_constant<2, 4, 8>(g.L, [&](auto ll) {
+      return with_constant<1, 2, 3, 4>(g.P, [&](auto p) {
+        constexpr int LL = decltype(ll)::value, P = decltype(p)::value;
+        hipLaunchKernelGGL((lva_step_fast<LL, P>), grid, dim3(8 * TS), 0, st, a, g, codes, trellis, hdr, items);
+        return (int)hipGetLastError();
+      });
+    });
   }
   if (e) return e;
   if (ev_mid && (e = (int)hipEventRecord((hipEvent_t)ev_mid, st))) return e;
-  if (g.L > 1) {   // fix-up pass: exits at once when the work list is empty
-    hipLaunchKernelGGL(lva_step_fixup, dim3(256), dim3(256), 0, st, a, g, codes, trellis, hdr, items);
-    e = (int)hipGetLastError();
-  }
-  return e;
+  // 2. the fix-up pass over the work list (exits at once when it is empty); L = 1 has no ties to resolve, no work list
+  if (g.L == 1) return 0;
+  if (g.lazy && small_list(g))     // one target per wavefront and pass: the pass is a chain of dependent round trips, so more
+    return with_constant<1, 2, 3, 4>(g.P, [&](auto p) {   // (mostly idle) wavefronts, not fewer
+      hipLaunchKernelGGL((lva_step_fixup_lazy<decltype(p)::value>), dim3(kFixupLazyGrid), dim3(256), 0, st, a, g, codes, trellis, hdr, items);
+      return (int)hipGetLastError();
+    });
+  hipLaunchKernelGGL(lva_step_fixup_wave, dim3(4096), dim3(256), 0, st, a, g, codes, trellis, hdr, items);
+  return (int)hipGetLastError();
 }
 
 int launch_prepare_step(const StepArgs& a, const DevCode* codes, SlotStep* steps, void* stream) {

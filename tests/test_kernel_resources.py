@@ -44,6 +44,18 @@ def test_register_and_lds_budgets(asm):
         assert v["vgpr"] <= 168 and v["lds"] <= 53 * 1024 and v["scratch"] == 0, (k, v)
     for k, v in pick(r"lva_step_acs").items():
         assert v["scratch"] == 0, (k, v)
+    # the exact paths, one wavefront per target (wave_merge): registers within the occupancy step they had before the merge was
+    # shared (VGPRs allocated in steps of 8; 64 / 96 / 128 = 8 / 5 / 4 wavefronts per SIMD), scratch no larger.
+    # lva_step_fixup_wave is held to 64 registers by its launch bounds; loading the compared words on every lane (no per-lane
+    # branch in front of the loads) costs it 8 bytes of spill slots there: 40 -> 48, spill reloads 22 -> 10
+    exact = {r"lva_step_fixup_waveE": (64, 48), r"lva_step_waveE": (64, 0),
+             r"lva_step_fixup_lazyILi1E": (96, 0), r"lva_step_fixup_lazyILi2E": (96, 0),
+             r"lva_step_fixup_lazyILi3E": (128, 0), r"lva_step_fixup_lazyILi4E": (128, 0)}
+    for pat, (vgpr, scratch) in exact.items():
+        got = pick(pat)
+        assert len(got) == 1, (pat, list(got))
+        for k, v in got.items():
+            assert v["vgpr"] <= vgpr and v["scratch"] <= scratch, (k, v)
 
 
 def test_big_list_output_phase_requests_a_round_at_once(asm):
