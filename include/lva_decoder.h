@@ -31,6 +31,8 @@ extern "C" {
 #define LVA_ERR_ARG (-10)
 #define LVA_ERR_NO_DEVICE (-11)      /* no gfx950 device visible: the product never falls back to CPU */
 #define LVA_ERR_UNSUPPORTED (-12)
+#define LVA_ERR_BUSY (-13)           /* lva_stream_submit: queue_cap reads already wait for a slot (back-pressure, nothing was taken);
+                                        any batch entry point or a second lva_stream_open while the decoder has a stream open */
 
 #define LVA_MAX_DEVIATION_DEFAULT 0xFFFFFFFFu /* reference default msg_len+mem_conv+1 (:238-240) */
 
@@ -72,7 +74,7 @@ typedef struct lva_code_info {
   uint8_t pattern[16];
 } lva_code_info;
 
-/* Counters of the last lva_decode_batch* call (bench.py's roofline object). */
+/* Counters of the last lva_decode_batch* call, or of the last stream after its close (bench.py's roofline object). */
 typedef struct lva_profile {
   double step_kernel_ms;      /* HIP-event time from first to last trellis-step launch, on the decoder's stream */
   double total_ms;            /* HIP-event time of the whole call's device work (upload..results) */
@@ -177,6 +179,39 @@ int lva_decoder_profile(const lva_decoder *d, lva_profile *out);
 /* on != 0: record HIP events around every trellis-step launch of later decode calls (three per launch, on the
  * decoder's stream) so that lva_profile carries per-kernel times measured live; off by default. */
 int lva_decoder_set_launch_events(lva_decoder *d, int32_t on);
+
+/* --- decode stream ------------------------------------------------------------------------
+ * A decoder that stays resident and is fed while it runs: reads go in one at a time, launches are shared by whatever is
+ * in flight, results come out as they finish.  A read's list and scores are those of lva_decode_batch, bit for bit,
+ * whenever it was submitted and whatever else is in flight.  The library starts no thread: lva_stream_poll drives the
+ * stream.  One stream per decoder; while it is open every batch entry point of that decoder (lva_decode_*, lva_basecall_*,
+ * lva_locate_payload_*, lva_find_barcode_batch) returns LVA_ERR_BUSY.
+ * replaces: the process per read of helper.py:305, simulator.py:85 and generate_decoded_lists.py:90, and the side-by-side
+ * driver copies the reference scales with (util/extra/generate_read_id_files.py:23-36, merge_lists.py:11-21). */
+typedef struct lva_stream lva_stream;
+
+/* queue_cap >= 1: reads that may wait for a slot.  Resets the decoder's profile counters. */
+int lva_stream_open(lva_decoder *d, int32_t queue_cap, lva_stream **out);
+/* Waits for what is enqueued on the device, drops reads that have not been handed out, frees the stream.  The decoder takes
+ * batch calls again; lva_decoder_profile then reports the stream's totals (launches, read-steps, algorithmic and working
+ * bytes, fix-up counters, overflow steps, event times from open to close; the per-launch event sums stay zero). */
+int lva_stream_close(lva_stream *s);
+/* One read: read_crf_post (:553-575) of a host float32 [n_blocks][40] matrix, copied before the call returns.  Never waits
+ * for a decode.  LVA_ERR_BUSY when queue_cap reads already wait for a slot (nothing taken: poll, then submit again).  A read
+ * the reference would refuse (n_blocks < nstate_pos + 1, :600-601) is accepted and comes back from lva_stream_poll with
+ * count LVA_ERR_POST_TOO_SHORT.  rc != 0: decode as reverse complement (--rc).  tag: the caller's name of the read. */
+int lva_stream_submit(lva_stream *s, const float *post, int64_t n_blocks, int32_t rc, uint64_t tag);
+/* decode_post_conv_parallel_LVA (:589-858) + the list writer (:248-253), a step at a time: enqueues launch groups while a
+ * slot is active (at most 32 launches ahead of the device), refills free slots from the queue in submission order, and hands
+ * out up to max_reads finished reads in the order they finished, in the layout of lva_decode_batch:
+ *   tags[k], out_msgs[k][list_size][msg_len] (rows >= count untouched), out_scores[k][list_size] (may be NULL),
+ *   out_counts[k] (entries, or a negative LVA_ERR_*); *n_out reads were written.
+ * wait = 0 never blocks on the device; wait = 1 returns as soon as at least one read is finished or nothing is pending. */
+int lva_stream_poll(lva_stream *s, int32_t wait, int32_t max_reads, uint64_t *tags, uint8_t *out_msgs, float *out_scores,
+                    int32_t *out_counts, int32_t *n_out);
+/* queued: waiting for a slot; in_slots: in a slot, or out of it with the result still on its way to the host;
+ * finished: ready for lva_stream_poll.  Each may be NULL. */
+int lva_stream_pending(const lva_stream *s, int32_t *queued, int32_t *in_slots, int32_t *finished);
 
 /* Device helpers so that callers without a HIP binding (ctypes) can keep inputs resident. */
 int lva_device_alloc(lva_decoder *d, uint64_t bytes, void **out_dev_ptr);

@@ -7,12 +7,14 @@ _LIB_NAME = "liblva_hip.so"
 
 MAX_DEVIATION_DEFAULT = 0xFFFFFFFF
 ABI_VERSION = 5                # LVA_ABI_VERSION of include/lva_decoder.h
+ERR_POST_TOO_SHORT = -6
+ERR_BUSY = -13
 
 ERRORS = {
     -1: "LVA_ERR_MEM_CONV", -2: "LVA_ERR_RATE", -3: "LVA_ERR_MSG_LEN", -4: "LVA_ERR_SYNC",
     -5: "LVA_ERR_TOO_MANY_STATES", -6: "LVA_ERR_POST_TOO_SHORT", -7: "LVA_ERR_MSG_TOO_LONG",
     -8: "LVA_ERR_NOMEM", -9: "LVA_ERR_HIP", -10: "LVA_ERR_ARG", -11: "LVA_ERR_NO_DEVICE",
-    -12: "LVA_ERR_UNSUPPORTED",
+    -12: "LVA_ERR_UNSUPPORTED", -13: "LVA_ERR_BUSY",
 }
 
 # every symbol include/lva_decoder.h declares
@@ -24,6 +26,7 @@ EXPORTS = [
     "lva_decode_windows_device", "lva_basecall_batch", "lva_basecall_batch_device", "lva_find_barcode_batch",
     "lva_locate_payload_batch", "lva_locate_payload_batch_device",
     "lva_rs_decode", "lva_rs_encode", "lva_rs_last_error",
+    "lva_stream_open", "lva_stream_close", "lva_stream_submit", "lva_stream_poll", "lva_stream_pending",
 ]
 
 
@@ -133,5 +136,13 @@ def load_library():
     L.lva_rs_decode.argtypes = [i32, vp, i32, i32, i32, vp, i32, u16, u16, vp, vp]
     L.lva_rs_encode.argtypes = [i32, vp, i32, i32, i32, u16, vp]
     L.lva_rs_last_error.restype = cp
+    if not hasattr(L, "lva_stream_open"):            # additive entry points: the ABI version did not change with them
+        raise ImportError("%s has no decode stream (lva_stream_open): rebuild it" % path)
+    i64 = ctypes.c_int64
+    L.lva_stream_open.argtypes = [vp, i32, ctypes.POINTER(vp)]
+    L.lva_stream_close.argtypes = [vp]
+    L.lva_stream_submit.argtypes = [vp, vp, i64, i32, u64]
+    L.lva_stream_poll.argtypes = [vp, i32, i32, vp, vp, vp, vp, ctypes.POINTER(i32)]
+    L.lva_stream_pending.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     _lib = L
     return L

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <limits>
 #include <numeric>
 #include <string>
@@ -41,6 +42,8 @@ thread_local std::string g_hip_error;
 
 }  // namespace
 
+struct lva_stream;
+
 struct lva_decoder {
   lva_config cfg{};
   std::string sync_marker;
@@ -68,6 +71,7 @@ struct lva_decoder {
   int launch_events = 0;       // lva_decoder_set_launch_events
   std::vector<hipEvent_t> ev_pool;
   lva_profile prof{};
+  lva_stream* open_stream = nullptr;   // lva_stream_open .. lva_stream_close: the batch entry points refuse meanwhile
 };
 
 namespace {
@@ -107,6 +111,7 @@ const char* lva_strerror(int code) {
     case LVA_ERR_ARG: return "invalid argument";
     case LVA_ERR_NO_DEVICE: return "no usable HIP device (the decoder has no CPU fallback)";
     case LVA_ERR_UNSUPPORTED: return "unsupported code structure";
+    case LVA_ERR_BUSY: return "busy: the stream's queue is full, or the decoder has a stream open";
     default: return "unknown error";
   }
 }
@@ -385,6 +390,7 @@ int lva_decoder_create(const lva_config* cfg, lva_decoder** out) {
 
 void lva_decoder_destroy(lva_decoder* d) {
   if (!d) return;
+  if (d->open_stream) (void)lva_stream_close(d->open_stream);
   (void)hipSetDevice(d->device);
   if (d->stream) (void)hipStreamSynchronize(d->stream);
   if (d->d_trellis) (void)hipFree(d->d_trellis);
@@ -449,6 +455,189 @@ static void finish_read(const lva_decoder* d, int orient, const uint32_t* rec, u
   *out_count = (int32_t)paths.size();
 }
 
+}  // extern "C"
+
+// band of every time step of one read (:677-679), evaluated here as the reference binary does: out[nb] = lo | hi << 16 (| lazy flags)
+static void read_band_table(const lva_decoder* d, const Code& c, uint32_t nb, uint32_t* out) {
+  // lazy mode: when was each position's row of either parity buffer last written?  Step t reads the buffer written
+  // by steps of t-1's parity; only the row of position lo-1 can be older than t-1 ("stale"), and at odd t
+  // its entries' messages live in the message buffer of the (even) step that wrote it
+  std::vector<int64_t> last_w[2];
+  if (d->g.lazy) { last_w[0].assign(c.npos + 1, -1); last_w[1].assign(c.npos + 1, -1); if (c.npos) last_w[1][0] = -1; }
+  for (uint32_t t = 0; t < nb; ++t) {
+    uint32_t lo, hi;
+    working_band(c, t, nb, d->max_dev, &lo, &hi);
+    uint32_t w = lo | (hi << 16);
+    if (d->g.lazy) {
+      const int pc = (int)((t + 1) & 1u);                // parity class of the steps that wrote step t's "prev" buffer: t-1
+      if (t >= 1 && lo >= 1) {
+        const int64_t lw = last_w[pc][lo - 1];
+        if (lw >= 0 && lw != (int64_t)t - 1) w |= 1u << 30 | (uint32_t)((lw >> 1) & 1) << 31;
+      }
+      for (uint32_t p = lo; p < hi; ++p) last_w[t & 1u][p] = t;
+    }
+    out[t] = w;
+  }
+}
+
+namespace {
+// The host schedule, written once for a batch call (decode_impl) and for a decode stream (lva_stream_poll): reads enter slots
+// (fill), one launch group advances every active slot by one time step (launch), finished reads leave through the gather
+// (retire).  Which read goes into which slot, and when, is the caller's: longest first for a batch, first in first served
+// for a stream.  A read's result depends on neither.
+struct Schedule {
+  struct Slot {
+    int32_t read = -1;         // the caller's name of the read in the slot
+    uint32_t end = 0;          // launch number after the read's last step
+    uint32_t nblk = 0, orient = 0;
+    uint32_t last_band = 0;    // band word of the last time step: was the final state ever written?
+    uint32_t rec = 0;          // result record the gather writes
+  };
+  lva_decoder* d;
+  std::vector<Slot> slot;
+  uint32_t* results;           // device, [records][8 L F words]
+  bool launch_events;
+  size_t active = 0;
+  size_t waiting = 0;          // slots whose read starts with the launch after next (lazy mode's phase alignment)
+  size_t ev_used = 0;
+  bool first_step = true;
+  InitBatch ib;
+  GatherBatch gb;
+
+  Schedule(lva_decoder* dec, size_t nslots, uint32_t* res, bool events) : d(dec), slot(nslots), results(res), launch_events(events) {
+    ib.n = 0; ib.pad = 0; gb.n = 0;
+  }
+  void reset_profile() {
+    lva_profile& p = d->prof;
+    p.step_launches = 0; p.read_steps = 0; p.algorithmic_bytes = 0; p.working_bytes = 0; p.fixup_states = 0; p.overflow_steps = 0;
+    p.dominant_kernel_ms = 0; p.step_pair_ms = 0; p.timed_launches = 0;
+  }
+  int next_event(hipEvent_t* out) {
+    if (ev_used == d->ev_pool.size()) {
+      hipEvent_t e;
+      HIP_TRY(hipEventCreate(&e));
+      d->ev_pool.push_back(e);
+    }
+    *out = d->ev_pool[ev_used++];
+    return LVA_OK;
+  }
+  int flush_inits() {
+    const int e = launch_init_slots(d->g, d->d_codes, d->d_trellis, ib, d->d_slots, d->stream);
+    ib.n = 0;
+    if (e) { g_hip_error = hipGetErrorString((hipError_t)e); return LVA_ERR_HIP; }
+    return LVA_OK;
+  }
+  int flush_gathers() {
+    const int e = launch_gather_finals(d->g, d->d_codes, d->d_trellis, gb, results, d->stream);
+    gb.n = 0;
+    if (e) { g_hip_error = hipGetErrorString((hipError_t)e); return LVA_ERR_HIP; }
+    return LVA_OK;
+  }
+  // a read enters idle slot s: its descriptor and initial scores (:657-663) go in stream order, a batch of slots per launch
+  // (behind the gathers of the reads that left them: retire runs before the next fill)
+  int fill(size_t s, int32_t read, const float* post_dev, const uint32_t* band_dev, uint32_t nblk, uint32_t orient, uint32_t last_band,
+           uint32_t rec) {
+    SlotDesc sd;
+    sd.post = post_dev;
+    sd.band = band_dev;
+    sd.nblk = nblk; sd.orient = orient;
+    // Lazy mode: every read starts on an EVEN launch (a read that arrives on an odd one idles for one launch: 1 in ~500),
+    // so all slots are at an even time step on even launches and at an odd one on odd launches -- a launch then runs ONE
+    // instance of lva_step_lazy over a grid without workgroups of the wrong kind (launch_step_fast, phase_aligned)
+    sd.start = d->launch_no + (d->kernel == 4 ? (d->launch_no & 1u) : 0u); sd.pad = 0;
+    Slot& sl = slot[s];
+    sl.read = read; sl.end = sd.start + sd.nblk; sl.nblk = nblk; sl.orient = orient; sl.last_band = last_band; sl.rec = rec;
+    if (sd.start != d->launch_no) ++waiting;
+    ib.slot[ib.n] = (uint32_t)s; ib.desc[ib.n] = sd;
+    if (++ib.n == (uint32_t)kTurnoverBatch) { const int st = flush_inits(); if (st) return st; }
+    d->prof.algorithmic_bytes += d->code[orient].algorithmic_bytes(nblk, d->g.L, d->max_dev);
+    d->prof.working_bytes += d->code[orient].working_bytes(nblk, d->g.L, d->max_dev);
+    ++active;
+    return LVA_OK;
+  }
+  // one launch group over slots [0, nslots): prepare, dominant kernel, fix-up
+  int launch(uint32_t nslots) {
+    const uint32_t npos = d->code[0].npos;
+    StepArgs a;
+    a.slots = d->d_slots; a.steps = d->d_steps; a.nslots = nslots; a.band_max = std::min<uint32_t>(npos, 2 * d->max_dev);
+    a.launch_no = d->launch_no; a.step_parity = d->launch_no & 1u;
+    a.phase_aligned = d->kernel == 4 ? 1u : 0u;
+    a.full_lo = d->full_lo; a.full_hi = d->full_hi; a.pad = 0;
+    {
+      const int e = launch_prepare_step(a, d->d_codes, d->d_steps, d->stream);
+      if (e) { g_hip_error = hipGetErrorString((hipError_t)e); return LVA_ERR_HIP; }
+    }
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+    if (launch_events) {
+      int st;
+      if ((st = next_event(&e0)) || (st = next_event(&e1)) || (st = next_event(&e2))) return st;
+      HIP_TRY(hipEventRecord(e0, d->stream));
+      if (first_step) HIP_TRY(hipEventRecord(d->ev_step0, d->stream));
+    } else if (first_step) {
+      HIP_TRY(hipEventRecord(d->ev_step0, d->stream));
+    }
+    first_step = false;
+    {
+      const int e = d->kernel == 2 || d->kernel == 4
+                        ? launch_step_fast(a, d->g, d->d_codes, d->d_trellis, d->d_work, reinterpret_cast<uint32_t*>(d->d_work + 1), d->stream, e1)
+                        : d->kernel == 3 ? launch_step_wave(a, d->g, d->d_codes, d->d_trellis, d->stream)
+                                         : launch_step_exact(a, d->g, d->d_codes, d->d_trellis, d->stream);
+      if (e) { g_hip_error = hipGetErrorString((hipError_t)e); return LVA_ERR_HIP; }
+    }
+    if (e2) {
+      if (d->kernel != 2 && d->kernel != 4) HIP_TRY(hipEventRecord(e1, d->stream));
+      HIP_TRY(hipEventRecord(e2, d->stream));
+    }
+    ++d->launch_no;
+    d->prof.step_launches += 1;
+    d->prof.read_steps += active - waiting;
+    waiting = 0;
+    return LVA_OK;
+  }
+  // reads whose last step was the launch just enqueued leave their slots: left(slot, gathered) for each; gathered = false
+  // when the final state was never written (an empty list, no record)
+  template <class F>
+  int retire(F&& left) {
+    const uint32_t npos = d->code[0].npos;
+    for (size_t s = 0; s < slot.size(); ++s) {
+      Slot& sl = slot[s];
+      if (sl.read < 0 || sl.end != d->launch_no) continue;
+      const bool got = (sl.last_band & 0xFFFFu) <= npos - 1 && npos - 1 < ((sl.last_band >> 16) & 0x3FFFu);
+      if (got) {
+        gb.a[gb.n] = GatherArgs{(uint32_t)s, (uint32_t)(sl.nblk & 1u), sl.orient, sl.rec, sl.nblk};
+        if (++gb.n == (uint32_t)kTurnoverBatch) { const int st = flush_gathers(); if (st) return st; }
+      }
+      left(sl, got);
+      sl.read = -1;
+      --active;
+    }
+    return flush_gathers();
+  }
+  // the totals a call or a stream leaves in the profile once the device is idle
+  int close_profile(const WorkHdr& h1) {
+    d->prof.fixup_states = h1.total;
+    d->prof.overflow_steps = h1.overflow_steps;
+    for (int i = 0; i < 4; ++i) d->prof.fixup_reason[i] = h1.reason[i];
+    float ms = 0;
+    if (!first_step) { HIP_TRY(hipEventElapsedTime(&ms, d->ev_step0, d->ev_step1)); }
+    d->prof.step_kernel_ms = ms;
+    HIP_TRY(hipEventElapsedTime(&ms, d->ev_total0, d->ev_total1));
+    d->prof.total_ms = ms;
+    for (size_t i = 0; i + 3 <= ev_used; i += 3) {
+      float a_ms = 0, b_ms = 0;
+      HIP_TRY(hipEventElapsedTime(&a_ms, d->ev_pool[i], d->ev_pool[i + 1]));
+      HIP_TRY(hipEventElapsedTime(&b_ms, d->ev_pool[i], d->ev_pool[i + 2]));
+      d->prof.dominant_kernel_ms += a_ms;
+      d->prof.step_pair_ms += b_ms;
+      d->prof.timed_launches += 1;
+    }
+    return LVA_OK;
+  }
+};
+}  // namespace
+
+extern "C" {
+
 static int decode_impl(lva_decoder* d, const float* post_dev, const int64_t* beg, const int64_t* len, int32_t n, const uint8_t* rc_flags,
                        uint8_t* out_msgs, float* out_scores, int32_t* out_counts, bool timed_total_started) {
   const Geometry& g = d->g;
@@ -480,35 +669,14 @@ static int decode_impl(lva_decoder* d, const float* post_dev, const int64_t* beg
   }
   if (!timed_total_started) HIP_TRY(hipEventRecord(d->ev_total0, d->stream));
 
-  // band of every time step of every read (:677-679), evaluated here as the reference binary does
   band.assign(std::max<size_t>(band_words, 1), 0u);
   std::vector<size_t> band_at((size_t)n, 0);
   {
     size_t at = 0;
     for (int32_t r : order) {
       band_at[(size_t)r] = at;
-      const Code& c = d->code[rc_flags && rc_flags[r] ? 1 : 0];
-      const uint32_t nb = (uint32_t)len[r];
-      // lazy mode: when was each position's row of either parity buffer last written?  Step t reads the buffer written
-      // by steps of t-1's parity; only the row of position lo-1 can be older than t-1 ("stale"), and at odd t
-      // its entries' messages live in the message buffer of the (even) step that wrote it
-      std::vector<int64_t> last_w[2];
-      if (d->g.lazy) { last_w[0].assign(c.npos + 1, -1); last_w[1].assign(c.npos + 1, -1); if (c.npos) last_w[1][0] = -1; }
-      for (uint32_t t = 0; t < nb; ++t) {
-        uint32_t lo, hi;
-        working_band(c, t, nb, d->max_dev, &lo, &hi);
-        uint32_t w = lo | (hi << 16);
-        if (d->g.lazy) {
-          const int pc = (int)((t + 1) & 1u);                // parity class of the steps that wrote step t's "prev" buffer: t-1
-          if (t >= 1 && lo >= 1) {
-            const int64_t lw = last_w[pc][lo - 1];
-            if (lw >= 0 && lw != (int64_t)t - 1) w |= 1u << 30 | (uint32_t)((lw >> 1) & 1) << 31;
-          }
-          for (uint32_t p = lo; p < hi; ++p) last_w[t & 1u][p] = t;
-        }
-        band[at + t] = w;
-      }
-      at += nb;
+      read_band_table(d, d->code[rc_flags && rc_flags[r] ? 1 : 0], (uint32_t)len[r], band.data() + at);
+      at += (size_t)len[r];
     }
   }
   if (band.size() > d->band_cap) {
@@ -523,135 +691,33 @@ static int decode_impl(lva_decoder* d, const float* post_dev, const int64_t* beg
   HIP_TRY(hipMemcpyAsync(d->d_work, &h0, sizeof h0, hipMemcpyHostToDevice, d->stream));
   HIP_TRY(hipMemsetAsync(d->d_slots, 0, (size_t)d->slots * sizeof(SlotDesc), d->stream));   // nblk = 0: no slot takes part yet
 
-  struct Slot { int32_t read = -1; uint32_t end = 0; };     // end: launch number after the read's last step
-  std::vector<Slot> slot((size_t)std::min<size_t>((size_t)d->slots, std::max<size_t>(order.size(), 1)));
+  Schedule sc(d, std::min<size_t>((size_t)d->slots, std::max<size_t>(order.size(), 1)), d->d_results, d->launch_events != 0);
+  sc.reset_profile();
   size_t next = 0;
   gathered.assign((size_t)n, 0);
-  d->prof.step_launches = 0; d->prof.read_steps = 0; d->prof.algorithmic_bytes = 0; d->prof.working_bytes = 0; d->prof.fixup_states = 0; d->prof.overflow_steps = 0;
-  d->prof.dominant_kernel_ms = 0; d->prof.step_pair_ms = 0; d->prof.timed_launches = 0;
-  const uint32_t band_max = std::min<uint32_t>(npos, 2 * d->max_dev);
-  bool first_step = true;
-  size_t active = 0, ev_used = 0;
-  auto next_event = [&](hipEvent_t* out) -> int {
-    if (ev_used == d->ev_pool.size()) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreate(&e));
-      d->ev_pool.push_back(e);
-    }
-    *out = d->ev_pool[ev_used++];
-    return LVA_OK;
-  };
-  InitBatch ib; GatherBatch gb;
-  ib.n = 0; ib.pad = 0; gb.n = 0;
-  auto flush_inits = [&]() -> int {
-    const int e = launch_init_slots(g, d->d_codes, d->d_trellis, ib, d->d_slots, d->stream);
-    ib.n = 0;
-    if (e) { g_hip_error = hipGetErrorString((hipError_t)e); return LVA_ERR_HIP; }
-    return LVA_OK;
-  };
-  auto flush_gathers = [&]() -> int {
-    const int e = launch_gather_finals(g, d->d_codes, d->d_trellis, gb, d->d_results, d->stream);
-    gb.n = 0;
-    if (e) { g_hip_error = hipGetErrorString((hipError_t)e); return LVA_ERR_HIP; }
-    return LVA_OK;
-  };
   for (;;) {
-    size_t waiting = 0;              // slots whose read starts with the next launch (lazy mode's phase alignment)
-    // (re)fill idle slots: the reads' descriptors and initial scores (:657-663) go in stream order, a batch of slots per launch
-    // (behind the gathers of the reads that left them: the retire loop below runs first)
-    for (size_t s = 0; s < slot.size(); ++s) {
-      if (slot[s].read >= 0 || next >= order.size()) continue;
+    // (re)fill idle slots in the batch's order; a read's result record is the read's index
+    for (size_t s = 0; s < sc.slot.size(); ++s) {
+      if (sc.slot[s].read >= 0 || next >= order.size()) continue;
       const int32_t r = order[next++];
-      SlotDesc sd;
-      sd.post = post_dev + (size_t)beg[r] * 40;
-      sd.band = d->d_band + band_at[(size_t)r];
-      sd.nblk = (uint32_t)len[r]; sd.orient = rc_flags && rc_flags[r] ? 1u : 0u;
-      // Lazy mode: every read starts on an EVEN launch (a read that arrives on an odd one idles for one launch: 1 in ~500),
-      // so all slots are at an even time step on even launches and at an odd one on odd launches -- a launch then runs ONE
-      // instance of lva_step_lazy over a grid without workgroups of the wrong kind (launch_step_fast, phase_aligned)
-      sd.start = d->launch_no + (d->kernel == 4 ? (d->launch_no & 1u) : 0u); sd.pad = 0;
-      slot[s].read = r; slot[s].end = sd.start + sd.nblk;
-      if (sd.start != d->launch_no) ++waiting;
-      ib.slot[ib.n] = (uint32_t)s; ib.desc[ib.n] = sd;
-      if (++ib.n == (uint32_t)kTurnoverBatch) { const int st = flush_inits(); if (st) return st; }
-      d->prof.algorithmic_bytes += d->code[sd.orient].algorithmic_bytes(sd.nblk, L, d->max_dev);
-      d->prof.working_bytes += d->code[sd.orient].working_bytes(sd.nblk, L, d->max_dev);
-      ++active;
+      const uint32_t nb = (uint32_t)len[r];
+      const int st = sc.fill(s, r, post_dev + (size_t)beg[r] * 40, d->d_band + band_at[(size_t)r], nb, rc_flags && rc_flags[r] ? 1u : 0u,
+                             band[band_at[(size_t)r] + nb - 1], (uint32_t)r);
+      if (st) return st;
     }
-    { const int st = flush_inits(); if (st) return st; }
-    if (active == 0) break;
-    StepArgs a;
-    a.slots = d->d_slots; a.steps = d->d_steps; a.nslots = (uint32_t)slot.size(); a.band_max = band_max;
-    a.launch_no = d->launch_no; a.step_parity = d->launch_no & 1u;
-    a.phase_aligned = d->kernel == 4 ? 1u : 0u;
-    a.full_lo = d->full_lo; a.full_hi = d->full_hi; a.pad = 0;
-    {
-      const int e = launch_prepare_step(a, d->d_codes, d->d_steps, d->stream);
-      if (e) { g_hip_error = hipGetErrorString((hipError_t)e); return LVA_ERR_HIP; }
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-    if (d->launch_events) {
-      int st;
-      if ((st = next_event(&e0)) || (st = next_event(&e1)) || (st = next_event(&e2))) return st;
-      HIP_TRY(hipEventRecord(e0, d->stream));
-      if (first_step) HIP_TRY(hipEventRecord(d->ev_step0, d->stream));
-    } else if (first_step) {
-      HIP_TRY(hipEventRecord(d->ev_step0, d->stream));
-    }
-    first_step = false;
-    {
-      const int e = d->kernel == 2 || d->kernel == 4
-                        ? launch_step_fast(a, g, d->d_codes, d->d_trellis, d->d_work, reinterpret_cast<uint32_t*>(d->d_work + 1), d->stream, e1)
-                        : d->kernel == 3 ? launch_step_wave(a, g, d->d_codes, d->d_trellis, d->stream)
-                                         : launch_step_exact(a, g, d->d_codes, d->d_trellis, d->stream);
-      if (e) { g_hip_error = hipGetErrorString((hipError_t)e); return LVA_ERR_HIP; }
-    }
-    if (e2) {
-      if (d->kernel != 2 && d->kernel != 4) HIP_TRY(hipEventRecord(e1, d->stream));
-      HIP_TRY(hipEventRecord(e2, d->stream));
-    }
-    ++d->launch_no;
-    d->prof.step_launches += 1;
-    d->prof.read_steps += active - waiting;
-    // retire finished reads
-    for (size_t s = 0; s < slot.size(); ++s) {
-      if (slot[s].read < 0 || slot[s].end != d->launch_no) continue;
-      const int32_t r = slot[s].read;
-      const uint32_t nb = (uint32_t)len[r], orient = rc_flags && rc_flags[r] ? 1u : 0u;
-      const uint32_t last = band[band_at[(size_t)r] + nb - 1];
-      if ((last & 0xFFFFu) <= npos - 1 && npos - 1 < ((last >> 16) & 0x3FFFu)) {   // otherwise the final state was never written: empty list
-        gb.a[gb.n] = GatherArgs{(uint32_t)s, (uint32_t)(nb & 1u), orient, (uint32_t)r, nb};
-        if (++gb.n == (uint32_t)kTurnoverBatch) { const int st = flush_gathers(); if (st) return st; }
-        gathered[(size_t)r] = 1;
-      }
-      slot[s].read = -1;
-      --active;
-    }
-    { const int st = flush_gathers(); if (st) return st; }
+    { const int st = sc.flush_inits(); if (st) return st; }
+    if (sc.active == 0) break;
+    { const int st = sc.launch((uint32_t)sc.slot.size()); if (st) return st; }
+    { const int st = sc.retire([&](const Schedule::Slot& sl, bool got) { if (got) gathered[(size_t)sl.read] = 1; }); if (st) return st; }
   }
-  if (!first_step) HIP_TRY(hipEventRecord(d->ev_step1, d->stream));
+  if (!sc.first_step) HIP_TRY(hipEventRecord(d->ev_step1, d->stream));
   host.assign((size_t)n * rec_words, 0u);
   if (n > 0) HIP_TRY(hipMemcpyAsync(host.data(), d->d_results, host.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
   HIP_TRY(hipMemcpyAsync(&h1, d->d_work, sizeof h1, hipMemcpyDeviceToHost, d->stream));
   HIP_TRY(hipEventRecord(d->ev_total1, d->stream));
   HIP_TRY(hipStreamSynchronize(d->stream));
   drain.armed = false;
-  d->prof.fixup_states = h1.total;
-  d->prof.overflow_steps = h1.overflow_steps;
-  for (int i = 0; i < 4; ++i) d->prof.fixup_reason[i] = h1.reason[i];
-  float ms = 0;
-  if (!first_step) { HIP_TRY(hipEventElapsedTime(&ms, d->ev_step0, d->ev_step1)); }
-  d->prof.step_kernel_ms = ms;
-  HIP_TRY(hipEventElapsedTime(&ms, d->ev_total0, d->ev_total1));
-  d->prof.total_ms = ms;
-  for (size_t i = 0; i + 3 <= ev_used; i += 3) {
-    float a_ms = 0, b_ms = 0;
-    HIP_TRY(hipEventElapsedTime(&a_ms, d->ev_pool[i], d->ev_pool[i + 1]));
-    HIP_TRY(hipEventElapsedTime(&b_ms, d->ev_pool[i], d->ev_pool[i + 2]));
-    d->prof.dominant_kernel_ms += a_ms;
-    d->prof.step_pair_ms += b_ms;
-    d->prof.timed_launches += 1;
-  }
+  { const int st = sc.close_profile(h1); if (st) return st; }
 
   for (int32_t i = 0; i < n; ++i) {
     if (out_counts[i] < 0) continue;
@@ -663,9 +729,300 @@ static int decode_impl(lva_decoder* d, const float* post_dev, const int64_t* beg
   return LVA_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Decode stream: the same schedule, fed while it runs.  No thread of its own: lva_stream_poll drives it.
+// ---------------------------------------------------------------------------------------------
+struct lva_stream {
+  lva_decoder* d = nullptr;
+  uint32_t queue_cap = 0;
+  Schedule* sch = nullptr;
+  size_t rec_words = 0;
+  // one pinned host buffer + one device buffer per read in flight: 40 floats per block, then one band word per block.  A buffer
+  // returns to the free list when its read's result has been seen on the host (so no copy from it can still be pending)
+  struct PostBuf { uint32_t* host = nullptr; uint32_t* dev = nullptr; size_t cap = 0; };
+  std::vector<PostBuf> bufs;
+  std::vector<int32_t> free_bufs;
+  struct Read { uint64_t tag = 0; int32_t buf = -1; uint32_t nblk = 0, orient = 0, rec = 0; bool gathered = false; };
+  std::vector<Read> reads;             // indexed by the read's id (Schedule::Slot::read)
+  std::vector<int32_t> free_reads;
+  std::deque<int32_t> queue;           // waiting for a slot, in submission order
+  // a mark = an event behind a launch group: the reads that retired with that group are finished when it has passed
+  struct Mark { hipEvent_t ev = nullptr; uint32_t launch_no = 0; std::vector<int32_t> reads; };
+  std::deque<Mark> marks;
+  std::vector<hipEvent_t> free_ev;
+  struct Finished { uint64_t tag; int32_t count; std::vector<uint8_t> msgs; std::vector<float> scores; };
+  std::deque<Finished> finished;
+  uint32_t* d_res = nullptr;           // result records on the device ...
+  uint32_t* h_res = nullptr;           // ... and their pinned host copies, one per read between fill and hand-out
+  std::vector<uint32_t> free_rec;
+  uint32_t done_launch = 0;            // launches the device is known to have passed
+  size_t in_marks = 0;                 // reads retired on the host whose records are still on their way
+  WorkHdr h0, h1;
+};
+
+namespace {
+constexpr uint32_t kStreamAhead = 32;  // launches the host may be ahead of the device: what a new read waits at most before it
+                                       // can join, and what poll(wait = 0) enqueues at most in one call
+constexpr uint32_t kStreamMarkEvery = 4;
+
+int stream_take_buf(lva_stream* s, size_t nblk, int32_t* out) {
+  for (size_t k = 0; k < s->free_bufs.size(); ++k) {
+    const int32_t b = s->free_bufs[k];
+    if (s->bufs[(size_t)b].cap >= nblk) {
+      s->free_bufs[k] = s->free_bufs.back();
+      s->free_bufs.pop_back();
+      *out = b;
+      return LVA_OK;
+    }
+  }
+  lva_stream::PostBuf pb;
+  pb.cap = (std::max<size_t>(nblk, 256) + 63) / 64 * 64;
+  if (hipHostMalloc(reinterpret_cast<void**>(&pb.host), pb.cap * 41 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) return LVA_ERR_NOMEM;
+  if (hipMalloc(reinterpret_cast<void**>(&pb.dev), pb.cap * 41 * sizeof(uint32_t)) != hipSuccess) { (void)hipHostFree(pb.host); return LVA_ERR_NOMEM; }
+  s->bufs.push_back(pb);
+  *out = (int32_t)s->bufs.size() - 1;
+  return LVA_OK;
+}
+
+void stream_release_read(lva_stream* s, int32_t id) {
+  lva_stream::Read& r = s->reads[(size_t)id];
+  if (r.buf >= 0) s->free_bufs.push_back(r.buf);
+  r.buf = -1;
+  s->free_reads.push_back(id);
+}
+
+// marks the device has passed: their reads' records are on the host -> final selection, hand-out queue
+int stream_reap(lva_stream* s, bool block_on_first) {
+  lva_decoder* d = s->d;
+  const uint32_t L = d->g.L, msg_len = d->code[0].msg_len;
+  while (!s->marks.empty()) {
+    lva_stream::Mark& m = s->marks.front();
+    if (block_on_first) {
+      HIP_TRY(hipEventSynchronize(m.ev));
+      block_on_first = false;
+    } else {
+      const hipError_t e = hipEventQuery(m.ev);
+      if (e == hipErrorNotReady) break;
+      if (e != hipSuccess) { g_hip_error = std::string("hipEventQuery: ") + hipGetErrorString(e); return LVA_ERR_HIP; }
+    }
+    s->done_launch = m.launch_no;
+    for (int32_t id : m.reads) {
+      const lva_stream::Read& r = s->reads[(size_t)id];
+      lva_stream::Finished f{r.tag, 0, {}, {}};
+      if (r.gathered) {
+        f.msgs.assign((size_t)L * msg_len, 0);
+        f.scores.assign(L, 0.f);
+        finish_read(d, (int)r.orient, s->h_res + (size_t)r.rec * s->rec_words, f.msgs.data(), f.scores.data(), &f.count);
+      }
+      s->finished.push_back(std::move(f));
+      s->free_rec.push_back(r.rec);
+      stream_release_read(s, id);
+      --s->in_marks;
+    }
+    s->free_ev.push_back(m.ev);
+    s->marks.pop_front();
+  }
+  return LVA_OK;
+}
+
+// enqueue launch groups while there is work and the host is less than kStreamAhead launches ahead of the device
+int stream_pump(lva_stream* s) {
+  lva_decoder* d = s->d;
+  Schedule& sc = *s->sch;
+  while ((sc.active > 0 || !s->queue.empty()) && d->launch_no - s->done_launch < kStreamAhead) {
+    // free slots take the queue's reads in submission order, lowest slot first; a read takes its result record with it
+    for (size_t k = 0; k < sc.slot.size() && !s->queue.empty() && !s->free_rec.empty() && sc.active < sc.slot.size(); ++k) {
+      if (sc.slot[k].read >= 0) continue;
+      const int32_t id = s->queue.front();
+      s->queue.pop_front();
+      lva_stream::Read& r = s->reads[(size_t)id];
+      r.rec = s->free_rec.back();
+      s->free_rec.pop_back();
+      const lva_stream::PostBuf& pb = s->bufs[(size_t)r.buf];
+      const int st = sc.fill(k, id, reinterpret_cast<const float*>(pb.dev), pb.dev + (size_t)r.nblk * 40, r.nblk, r.orient,
+                             pb.host[(size_t)r.nblk * 40 + r.nblk - 1], r.rec);
+      if (st) return st;
+    }
+    { const int st = sc.flush_inits(); if (st) return st; }
+    if (sc.active == 0) break;
+    uint32_t nslots = 0;
+    for (size_t k = sc.slot.size(); k > 0; --k)
+      if (sc.slot[k - 1].read >= 0) { nslots = (uint32_t)k; break; }
+    { const int st = sc.launch(nslots); if (st) return st; }
+    lva_stream::Mark m;
+    {
+      const int st = sc.retire([&](const Schedule::Slot& sl, bool got) {
+        s->reads[(size_t)sl.read].gathered = got;
+        m.reads.push_back(sl.read);
+      });
+      if (st) return st;
+    }
+    if (m.reads.empty() && d->launch_no % kStreamMarkEvery != 0) continue;
+    // from here on the retired reads belong to the mark: on an error they are dropped with the stream (close drains)
+    for (int32_t id : m.reads) {
+      const lva_stream::Read& r = s->reads[(size_t)id];
+      if (r.gathered)
+        HIP_TRY(hipMemcpyAsync(s->h_res + (size_t)r.rec * s->rec_words, s->d_res + (size_t)r.rec * s->rec_words,
+                               s->rec_words * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    }
+    if (s->free_ev.empty()) {
+      hipEvent_t e;
+      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      s->free_ev.push_back(e);
+    }
+    m.ev = s->free_ev.back();
+    s->free_ev.pop_back();
+    m.launch_no = d->launch_no;
+    s->in_marks += m.reads.size();
+    const hipError_t e = hipEventRecord(m.ev, d->stream);
+    s->marks.push_back(std::move(m));
+    if (e != hipSuccess) { g_hip_error = std::string("hipEventRecord: ") + hipGetErrorString(e); return LVA_ERR_HIP; }
+  }
+  return LVA_OK;
+}
+}  // namespace
+
+int lva_stream_open(lva_decoder* d, int32_t queue_cap, lva_stream** out) {
+  if (!d || !out || queue_cap < 1) return LVA_ERR_ARG;
+  *out = nullptr;
+  if (d->open_stream) return LVA_ERR_BUSY;
+  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
+  lva_stream* s = new (std::nothrow) lva_stream();
+  if (!s) return LVA_ERR_NOMEM;
+  s->d = d;
+  s->queue_cap = (uint32_t)queue_cap;
+  s->rec_words = (size_t)8 * d->g.L * d->g.F;
+  const size_t nrec = 2 * (size_t)d->slots + kTurnoverBatch;
+  auto fail = [&](int code) {
+    (void)hipStreamSynchronize(d->stream);
+    if (s->d_res) (void)hipFree(s->d_res);
+    if (s->h_res) (void)hipHostFree(s->h_res);
+    delete s->sch;
+    delete s;
+    return code;
+  };
+  if (hipMalloc(reinterpret_cast<void**>(&s->d_res), nrec * s->rec_words * sizeof(uint32_t)) != hipSuccess) return fail(LVA_ERR_NOMEM);
+  if (hipHostMalloc(reinterpret_cast<void**>(&s->h_res), nrec * s->rec_words * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
+    return fail(LVA_ERR_NOMEM);
+  for (size_t i = nrec; i > 0; --i) s->free_rec.push_back((uint32_t)(i - 1));
+  s->sch = new (std::nothrow) Schedule(d, (size_t)d->slots, s->d_res, false);   // (per-launch events are a batch call's: a stream has no last launch to sum at)
+  if (!s->sch) return fail(LVA_ERR_NOMEM);
+  s->sch->reset_profile();
+  d->prof.h2d_ms = 0; d->prof.h2d_bytes = 0;
+  std::memset(&s->h0, 0, sizeof s->h0);
+  s->h0.cap = d->work_cap;
+  hipError_t e = hipEventRecord(d->ev_total0, d->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d->d_work, &s->h0, sizeof s->h0, hipMemcpyHostToDevice, d->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d->d_slots, 0, (size_t)d->slots * sizeof(SlotDesc), d->stream);   // nblk = 0: no slot takes part yet
+  if (e != hipSuccess) { g_hip_error = hipGetErrorString(e); return fail(LVA_ERR_HIP); }
+  s->done_launch = d->launch_no;
+  d->open_stream = s;
+  *out = s;
+  return LVA_OK;
+}
+
+int lva_stream_close(lva_stream* s) {
+  if (!s) return LVA_ERR_ARG;
+  lva_decoder* d = s->d;
+  (void)hipSetDevice(d->device);
+  // what is enqueued runs to its end (the pinned buffers below are targets and sources of its copies); reads that have not
+  // finished are dropped: a later call re-initialises the slots it uses
+  int st = LVA_OK;
+  hipError_t e = hipSuccess;
+  if (!s->sch->first_step) e = hipEventRecord(d->ev_step1, d->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(&s->h1, d->d_work, sizeof s->h1, hipMemcpyDeviceToHost, d->stream);
+  if (e == hipSuccess) e = hipEventRecord(d->ev_total1, d->stream);
+  const hipError_t e_sync = hipStreamSynchronize(d->stream);
+  if (e == hipSuccess) e = e_sync;
+  if (e != hipSuccess) { g_hip_error = hipGetErrorString(e); st = LVA_ERR_HIP; }
+  else st = s->sch->close_profile(s->h1);
+  for (lva_stream::Mark& m : s->marks) (void)hipEventDestroy(m.ev);
+  for (hipEvent_t ev : s->free_ev) (void)hipEventDestroy(ev);
+  for (lva_stream::PostBuf& pb : s->bufs) { (void)hipFree(pb.dev); (void)hipHostFree(pb.host); }
+  (void)hipFree(s->d_res);
+  (void)hipHostFree(s->h_res);
+  d->open_stream = nullptr;
+  delete s->sch;
+  delete s;
+  return st;
+}
+
+int lva_stream_submit(lva_stream* s, const float* post, int64_t n_blocks, int32_t rc, uint64_t tag) {
+  if (!s || n_blocks < 0 || n_blocks > 0xFFFFFFFFll || (n_blocks > 0 && !post)) return LVA_ERR_ARG;
+  lva_decoder* d = s->d;
+  const uint32_t npos = d->code[0].npos;
+  if ((uint64_t)n_blocks < (uint64_t)npos + 1) {           // (:600-601) comes back from poll like every other read
+    s->finished.push_back(lva_stream::Finished{tag, LVA_ERR_POST_TOO_SHORT, {}, {}});
+    return LVA_OK;
+  }
+  if (s->queue.size() >= s->queue_cap) return LVA_ERR_BUSY;
+  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
+  const uint32_t nb = (uint32_t)n_blocks, orient = rc ? 1u : 0u;
+  int32_t buf = -1;
+  { const int st = stream_take_buf(s, nb, &buf); if (st) return st; }
+  const lva_stream::PostBuf& pb = s->bufs[(size_t)buf];
+  std::memcpy(pb.host, post, (size_t)nb * 40 * sizeof(float));
+  read_band_table(d, d->code[orient], nb, pb.host + (size_t)nb * 40);
+  const hipError_t e = hipMemcpyAsync(pb.dev, pb.host, (size_t)nb * 41 * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream);
+  if (e != hipSuccess) {
+    // (the buffer is not reused: whether the copy was enqueued is unknown; it is freed at close, behind the drain)
+    g_hip_error = std::string("hipMemcpyAsync: ") + hipGetErrorString(e);
+    return LVA_ERR_HIP;
+  }
+  d->prof.h2d_bytes += (uint64_t)nb * 40 * sizeof(float);
+  int32_t id;
+  if (!s->free_reads.empty()) { id = s->free_reads.back(); s->free_reads.pop_back(); }
+  else { s->reads.emplace_back(); id = (int32_t)s->reads.size() - 1; }
+  lva_stream::Read& r = s->reads[(size_t)id];
+  r.tag = tag; r.buf = buf; r.nblk = nb; r.orient = orient; r.rec = 0; r.gathered = false;
+  s->queue.push_back(id);
+  return LVA_OK;
+}
+
+int lva_stream_poll(lva_stream* s, int32_t wait, int32_t max_reads, uint64_t* tags, uint8_t* out_msgs, float* out_scores,
+                    int32_t* out_counts, int32_t* n_out) {
+  if (!s || !n_out || max_reads < 0 || (max_reads > 0 && (!tags || !out_msgs || !out_counts))) return LVA_ERR_ARG;
+  *n_out = 0;
+  lva_decoder* d = s->d;
+  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
+  const size_t row = (size_t)d->g.L * d->code[0].msg_len;
+  bool block = false;
+  for (;;) {
+    { const int st = stream_reap(s, block); if (st) return st; }
+    { const int st = stream_pump(s); if (st) return st; }
+    if (!block) { const int st = stream_reap(s, false); if (st) return st; }   // (what finished while the launches were enqueued)
+    if (!s->finished.empty() || !wait || max_reads == 0) break;
+    if (s->marks.empty()) break;       // nothing pending: every read handed in has been handed out
+    block = true;                      // wait = 1: sleep on the oldest mark, then look again
+  }
+  int32_t k = 0;
+  while (k < max_reads && !s->finished.empty()) {
+    lva_stream::Finished& f = s->finished.front();
+    tags[k] = f.tag;
+    out_counts[k] = f.count;
+    if (f.count > 0) {
+      std::memcpy(out_msgs + (size_t)k * row, f.msgs.data(), (size_t)f.count * d->code[0].msg_len);
+      if (out_scores) std::memcpy(out_scores + (size_t)k * d->g.L, f.scores.data(), (size_t)f.count * sizeof(float));
+    }
+    s->finished.pop_front();
+    ++k;
+  }
+  *n_out = k;
+  return LVA_OK;
+}
+
+int lva_stream_pending(const lva_stream* s, int32_t* queued, int32_t* in_slots, int32_t* finished) {
+  if (!s) return LVA_ERR_ARG;
+  if (queued) *queued = (int32_t)s->queue.size();
+  if (in_slots) *in_slots = (int32_t)(s->sch->active + s->in_marks);
+  if (finished) *finished = (int32_t)s->finished.size();
+  return LVA_OK;
+}
+
 int lva_decode_batch_device(lva_decoder* d, const float* post_dev, const int64_t* row_offsets, int32_t n_reads,
                             const uint8_t* rc_flags, uint8_t* out_msgs, float* out_scores, int32_t* out_counts) {
   if (!d || n_reads < 0 || !row_offsets || (n_reads > 0 && (!post_dev || !out_msgs || !out_counts))) return LVA_ERR_ARG;
+  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
   if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
   std::vector<int64_t> len((size_t)n_reads);
   for (int32_t i = 0; i < n_reads; ++i) len[i] = row_offsets[i + 1] - row_offsets[i];
@@ -676,6 +1033,7 @@ int lva_decode_windows_device(lva_decoder* d, const float* post_dev, const int64
                               int32_t n_reads, const uint8_t* rc_flags, uint8_t* out_msgs, float* out_scores,
                               int32_t* out_counts) {
   if (!d || n_reads < 0 || (n_reads > 0 && (!post_dev || !first_block || !n_blocks || !out_msgs || !out_counts))) return LVA_ERR_ARG;
+  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
   if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
   return decode_impl(d, post_dev, first_block, n_blocks, n_reads, rc_flags, out_msgs, out_scores, out_counts, false);
 }
@@ -683,6 +1041,7 @@ int lva_decode_windows_device(lva_decoder* d, const float* post_dev, const int64
 int lva_decode_batch(lva_decoder* d, const float* post, const int64_t* row_offsets, int32_t n_reads,
                      const uint8_t* rc_flags, uint8_t* out_msgs, float* out_scores, int32_t* out_counts) {
   if (!d || n_reads < 0 || !row_offsets || (n_reads > 0 && (!post || !out_msgs || !out_counts))) return LVA_ERR_ARG;
+  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
   if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
   const int64_t blocks = n_reads > 0 ? row_offsets[n_reads] : 0;
   if (blocks < 0) return LVA_ERR_ARG;
@@ -845,6 +1204,7 @@ extern "C" {
 int lva_basecall_batch_device(lva_decoder* d, const float* post_dev, const int64_t* row_offsets, int32_t n_reads,
                               char* bases_out, uint32_t* trans_out, int32_t* nbases_out) {
   if (!d || n_reads < 0 || !row_offsets || (n_reads > 0 && (!post_dev || !nbases_out))) return LVA_ERR_ARG;
+  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
   if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
   return bc_run(d, post_dev, row_offsets, n_reads, nullptr, 0, 0, bases_out, trans_out, nbases_out, nullptr);
 }
@@ -852,6 +1212,7 @@ int lva_basecall_batch_device(lva_decoder* d, const float* post_dev, const int64
 int lva_basecall_batch(lva_decoder* d, const float* post, const int64_t* row_offsets, int32_t n_reads, char* bases_out,
                        uint32_t* trans_out, int32_t* nbases_out) {
   if (!d || n_reads < 0 || !row_offsets || (n_reads > 0 && (!post || !nbases_out))) return LVA_ERR_ARG;
+  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
   if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
   HostPost hp;
   const int st = upload_post(d, post, row_offsets, n_reads, &hp);
@@ -863,6 +1224,7 @@ int lva_locate_payload_batch_device(lva_decoder* d, const float* post_dev, const
                                     const char* start_barcode, const char* end_barcode, uint32_t min_len,
                                     lva_payload_pos* out) {
   if (!d || n_reads < 0 || !row_offsets || (n_reads > 0 && (!post_dev || !out))) return LVA_ERR_ARG;
+  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
   if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
   BcPatterns pat;
   const int st = make_patterns(start_barcode, end_barcode, 2, &pat);
@@ -873,6 +1235,7 @@ int lva_locate_payload_batch_device(lva_decoder* d, const float* post_dev, const
 int lva_locate_payload_batch(lva_decoder* d, const float* post, const int64_t* row_offsets, int32_t n_reads,
                              const char* start_barcode, const char* end_barcode, uint32_t min_len, lva_payload_pos* out) {
   if (!d || n_reads < 0 || !row_offsets || (n_reads > 0 && (!post || !out))) return LVA_ERR_ARG;
+  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
   if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
   BcPatterns pat;
   int st = make_patterns(start_barcode, end_barcode, 2, &pat);
@@ -886,6 +1249,7 @@ int lva_locate_payload_batch(lva_decoder* d, const float* post, const int64_t* r
 int lva_find_barcode_batch(lva_decoder* d, const char* bases, const uint32_t* trans, const int64_t* base_offsets,
                            int32_t n_reads, const char* start_barcode, const char* end_barcode, lva_payload_pos* out) {
   if (!d || n_reads < 0 || !base_offsets || (n_reads > 0 && (!bases || !trans || !out))) return LVA_ERR_ARG;
+  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
   if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
   if (n_reads == 0) return LVA_OK;
   BcPatterns pat;

@@ -314,6 +314,37 @@ class Decoder:
             out[i] = (loc[i], r)
         return out
 
+    # --- decode stream: reads go in one at a time, results come out as they finish -------------
+    def stream(self, queue_cap=None):
+        """A DecodeStream on this decoder (a context manager).  queue_cap: reads that may wait for a slot before submit()
+        reports back-pressure (default: the slot count).  While it is open decode() and the other batch methods raise."""
+        return DecodeStream(self, queue_cap)
+
+    def decode_iter(self, posts, rc=None):
+        """Generator: submits from the iterable `posts` (and `rc`, an iterable of bools, or None) as back-pressure allows and
+        yields (index, result) as reads finish -- result as decode() gives it; the next matrices are fetched from the iterable
+        while earlier reads decode."""
+        rcs = None if rc is None else iter(rc)
+        it = enumerate(posts)
+        with self.stream() as st:
+            held = None
+            more = True
+            while more or held is not None or st.outstanding:
+                while more or held is not None:
+                    if held is None:
+                        try:
+                            i, p = next(it)
+                        except StopIteration:
+                            more = False
+                            break
+                        held = (i, p, bool(next(rcs)) if rcs is not None else False)
+                    if not st.submit(held[1], rc=held[2], tag=held[0]):
+                        break                                  # queue full: hand out what has finished first
+                    held = None
+                # block only when nothing more can go in before a read comes out
+                for tag, res in st.poll(wait=held is not None or not more):
+                    yield tag, res
+
     def set_launch_events(self, on=True):
         """HIP events around every trellis-step launch of later decode calls (profile(): dominant_kernel_ms, step_pair_ms)"""
         self._check(self._L.lva_decoder_set_launch_events(self._h, int(bool(on))))
@@ -324,3 +355,79 @@ class Decoder:
         d = {k: getattr(p, k) for k, _ in _lib.Profile._fields_}
         d["fixup_reason"] = list(p.fixup_reason)
         return d
+
+
+class DecodeStream:
+    """lva_stream_* of include/lva_decoder.h.  submit() hands one read in, poll() drives the device and hands finished reads out
+    (in the order they finish).  Tags are the caller's names of the reads: any Python object (default: a running number)."""
+
+    def __init__(self, dec, queue_cap=None):
+        self._dec, self._L = dec, dec._L
+        self.slots = dec.profile()["slots"]
+        self.queue_cap = int(self.slots if queue_cap is None else queue_cap)
+        h = ctypes.c_void_p()
+        dec._check(self._L.lva_stream_open(dec._h, self.queue_cap, ctypes.byref(h)))
+        self._h = h
+        self._tags = {}
+        self._next = 0
+        n = self._cap = max(16, min(self.slots, 1024))
+        self._otags = np.zeros(n, np.uint64)
+        self._msgs, self._scores, self._counts = dec._outputs(n)
+
+    @property
+    def outstanding(self):
+        """reads submitted and not yet handed out by poll()"""
+        return len(self._tags)
+
+    def submit(self, post, rc=False, tag=None):
+        """One read: float32 [nblk, 40] (.post layout), copied before the call returns.  -> True, or False when queue_cap reads
+        already wait for a slot (nothing was taken: poll(), then submit again)."""
+        p = np.ascontiguousarray(post, dtype=np.float32).reshape(-1, 40)
+        key = self._next
+        st = self._L.lva_stream_submit(self._h, p.ctypes.data, p.shape[0], int(bool(rc)), key)
+        if st == _lib.ERR_BUSY:
+            return False
+        self._dec._check(st)
+        self._next += 1
+        self._tags[key] = key if tag is None else tag
+        return True
+
+    def poll(self, wait=False):
+        """-> [(tag, (msgs, scores) | negative code)] of reads that have finished.  wait=False never blocks on the device;
+        wait=True returns as soon as at least one read is finished or nothing is pending."""
+        out = []
+        while True:
+            n = ctypes.c_int32(0)
+            self._dec._check(self._L.lva_stream_poll(self._h, int(bool(wait)) if not out else 0, self._cap, self._otags.ctypes.data,
+                                                     self._msgs.ctypes.data, self._scores.ctypes.data, self._counts.ctypes.data,
+                                                     ctypes.byref(n)))
+            for k, res in enumerate(self._dec._unpack(n.value, self._msgs, self._scores, self._counts)):
+                out.append((self._tags.pop(int(self._otags[k])), res))
+            if n.value < self._cap:
+                return out
+
+    def pending(self):
+        """-> dict(queued, in_slots, finished): waiting for a slot / being decoded / ready for poll()"""
+        q, a, f = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        self._dec._check(self._L.lva_stream_pending(self._h, ctypes.byref(q), ctypes.byref(a), ctypes.byref(f)))
+        return dict(queued=q.value, in_slots=a.value, finished=f.value)
+
+    def close(self):
+        """drains the device, drops reads that were not handed out; the decoder takes batch calls again"""
+        if self._h is not None and getattr(self._dec, "_h", None):
+            h, self._h = self._h, None
+            self._tags.clear()
+            self._dec._check(self._L.lva_stream_close(h))
+        self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover
+            pass

@@ -101,9 +101,10 @@ def decode_rows(args, rows, dec):
     # rows with a window from an earlier search (:76, :84)
     keep = [i for i, r in enumerate(rows) if r[3] is not None and not (r[3] == -1 or r[4] - r[3] + 1 < min_len)]
     if keep:
-        posts = [helper.truncate_post(helper.read_post_file(rows[i][2]), rows[i][3], rows[i][4]) for i in keep]
-        for i, res in zip(keep, dec.decode(posts, rc=[rows[i][5] for i in keep])):
-            results[i] = res
+        # through a decode stream: the next .post files are read while earlier reads decode
+        posts = (helper.truncate_post(helper.read_post_file(rows[i][2]), rows[i][3], rows[i][4]) for i in keep)
+        for j, res in dec.decode_iter(posts, rc=(rows[i][5] for i in keep)):
+            results[keep[j]] = res
     return results, located
 
 

@@ -14,13 +14,19 @@ allocation every time (measured in DESIGN.md): batch callers should use Decoder.
 generate_decoded_lists, which keep one decoder for all reads.  Callers of the reference pass '' as an
 argv element when the read is not reverse-complemented (simulator.py:82-85); it is ignored here
 as cxxopts ignores it.
+
+With LVA_DECODE_SERVER=<socket path> in the environment the command line is forwarded to a resident decode_server
+(decode_client.request) and its answer returned: no decoder is created here.  The launcher viterbi/viterbi_nanopore.out
+then starts decode_client.py by file path instead of this module, so that a client process imports nothing but the
+standard library.
 """
 import argparse
+import os
 import sys
 
 import numpy as np
 
-from . import helper
+from . import decode_client, helper
 from ._lib import LvaError
 from .decoder import Decoder, bases_to_str, code_info, encode, str_to_bits
 
@@ -85,23 +91,27 @@ def _parse(argv):
     return p.parse_args([a for a in argv if a != ""])
 
 
-def main(argv=None, out=sys.stdout):
-    a = _parse(sys.argv[1:] if argv is None else argv)
+def front(argv, out, cwd=None):
+    """Everything the executable does before it needs a decoder: options, parameter checks, `-m encode`.
+    -> (exit code, None), or (None, (options, rc)) for a decode that may go ahead.  cwd: what relative paths are relative to."""
+    a = _parse(argv)
     if a.help:
         print(USAGE, file=out)
-        return 0
+        return 0, None
     if not a.mode or not a.infile or not a.outfile:
         print("Invalid options.", file=out); print(USAGE, file=out)
-        return 255
+        return 255, None
     if a.mode not in ("encode", "decode"):
         print("Invalid mode.", file=out); print(USAGE, file=out)
-        return 255
+        return 255, None
     if a.mem_conv is None:
         print("Memory of convolutional code not specified.", file=out); print(USAGE, file=out)
-        return 255
+        return 255, None
     if a.msg_len is None:
         print("msg-len not specified.", file=out); print(USAGE, file=out)
-        return 255
+        return 255, None
+    if cwd is not None:
+        a.infile, a.outfile = os.path.join(cwd, a.infile), os.path.join(cwd, a.outfile)
     rc = a.rc and a.mode == "decode"
     if rc:
         print("Reverse complement flag detected.", file=out)
@@ -109,25 +119,42 @@ def main(argv=None, out=sys.stdout):
         code_info(a.mem_conv, a.rate, a.msg_len, rc, a.sync_marker, a.sync_period)
     except LvaError as e:
         print(_PARAM_MESSAGES.get(e.code, str(e)), file=out); print(USAGE, file=out)
-        return 255
+        return 255, None
 
     if a.mode == "encode":
         msgs = []
         with open(a.infile) as f:                 # read_bit_array (:501-524)
             for line in f.read().split("\n")[:-1]:
                 if any(ch not in "01" for ch in line):
-                    return 134                    # "invalid character in input file"
+                    return 134, None              # "invalid character in input file"
                 msgs.append(line)
         for m in msgs:
             if len(m) != a.msg_len:
                 print("Message length does not match msg_len parameter.", file=out)
-                return 255
+                return 255, None
         with open(a.outfile, "w") as f:
             if msgs:
                 oligos = encode(a.mem_conv, a.rate, a.msg_len, np.stack([str_to_bits(m) for m in msgs]))
                 for o in oligos:
                     f.write(bases_to_str(o) + "\n")
-        return 0
+        return 0, None
+    return None, (a, rc)
+
+
+def write_list(path, msgs):
+    with open(path, "w") as f:                    # :248-253
+        for row in msgs:
+            f.write("".join("1" if b else "0" for b in row) + "\n")
+
+
+def main(argv=None, out=sys.stdout):
+    argv = sys.argv[1:] if argv is None else argv
+    if os.environ.get(decode_client.ENV):
+        return decode_client.request(argv, out)
+    code, job = front(argv, out)
+    if code is not None:
+        return code
+    a, rc = job
 
     try:
         post = helper.read_post_file(a.infile)
@@ -146,9 +173,7 @@ def main(argv=None, out=sys.stdout):
         return 1
     if isinstance(res, int):
         return 134                                # "Too small post matrix"
-    with open(a.outfile, "w") as f:               # :248-253
-        for row in res[0]:
-            f.write("".join("1" if b else "0" for b in row) + "\n")
+    write_list(a.outfile, res[0])
     return 0
 
 
