@@ -55,7 +55,8 @@ typedef struct lva_config {
   int32_t kernel;           /* 0 = default (4 where it is the faster one, else 2 where available, else 3, else 1);
                                1 = exact kernel, one thread per target; 2 = fast kernel + exact fix-up (L = 1, 2, 4, 8:
                                lva_step_fast / lva_step_acs; any other 2 <= L <= 64: lva_step_big); 3 = exact kernel, one
-                               wavefront per target (2 <= L <= 64); 4 = fast kernel with lazy messages (L = 2, 4, 8:
+                               wavefront per target (2 <= L <= 256: lva_step_wave up to 64 entries, lva_step_wave_wide
+                               above; never the default above 64, which stays 1); 4 = fast kernel with lazy messages (L = 2, 4, 8:
                                messages materialised every second time step, lva_step_lazy).  Every mode gives the
                                reference's lists bit for bit on every input the reference decodes: targets the fast
                                kernels cannot decide (score ties, non-finite sums, fingerprint collisions) go through a

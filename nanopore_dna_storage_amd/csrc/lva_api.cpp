@@ -371,8 +371,9 @@ int lva_decoder_create(const lva_config* cfg, lva_decoder** out) {
   d->prof.slots = slots;
   const bool fast_ok = fast_kernel_available(d->g);
   if (cfg->kernel == 2 && !fast_ok) return fail(LVA_ERR_UNSUPPORTED);
-  // 1 = exact (one thread per target), 2 = fast + fix-up, 3 = wavefront per target (lists of 9..64 entries)
-  if (cfg->kernel == 3 && !wave_kernel_available(d->g)) return fail(LVA_ERR_UNSUPPORTED);
+  // 1 = exact (one thread per target), 2 = fast + fix-up, 3 = wavefront per target (lists of 2..64 entries, and on request
+  // the wide kernel for 65..256: the default below consults the narrow predicate only, so above 64 entries it stays 1)
+  if (cfg->kernel == 3 && !wave_kernel_available(d->g) && !wave_wide_kernel_available(d->g)) return fail(LVA_ERR_UNSUPPORTED);
   d->kernel = cfg->kernel == 1 ? 1 : cfg->kernel == 3 ? 3 : lazy ? 4 : (fast_ok ? 2 : (wave_kernel_available(d->g) ? 3 : 1));
   if (d->kernel == 4 && (!fast_ok || c.nconv < 64)) return fail(LVA_ERR_UNSUPPORTED);
   d->prof.kernel = d->kernel;

@@ -14,6 +14,7 @@ bool fast_kernel_available(const Geometry& g);
 // whole step with the wavefront-per-target literal merge (2 <= L <= 64)
 int launch_step_wave(const StepArgs& a, const Geometry& g, const DevCode* codes, uint32_t* trellis, void* stream);
 bool wave_kernel_available(const Geometry& g);
+bool wave_wide_kernel_available(const Geometry& g);   // lists of 65..256 entries: launch_step_wave runs lva_step_wave_wide
 // this launch's SlotStep records (a.steps), to be enqueued right before the step launch
 int launch_prepare_step(const StepArgs& a, const DevCode* codes, SlotStep* steps, void* stream);
 // initial scores of up to kTurnoverBatch slots + their descriptors (the reads enter their slots); no launch for an empty batch

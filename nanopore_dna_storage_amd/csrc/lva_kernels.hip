@@ -26,6 +26,8 @@
 //   lva_step_fixup_wave   the exact path behind lva_step_fast and the big-list kernels: wave_target (one wavefront per
 //                    queued target, wave_merge) over the work list.
 //   lva_step_wave    wave_target over the whole step (kernel mode 3).
+//   lva_step_wave_wide<R>   the same for list sizes 65..256: R = 2, 3, 4 register rows of 64 entries per candidate list and for
+//                    the accepted entries (kernel mode 3 above 64 entries; on request only).
 //   lva_step_exact   one thread per target state, the same literal merge straight from HBM -- any list size; kernel
 //                    mode 1 and the default above 64 entries.
 //   lva_prepare_step per launch: slot descriptor -> this launch's SlotStep record of every slot
@@ -516,28 +518,60 @@ __global__ __launch_bounds__(256) void lva_step_exact(StepArgs args, Geometry g,
 namespace {
 
 // ---------------------------------------------------------------------------------------
-// The reference's k-way merge of ONE target by ONE WAVEFRONT (:743-800), list sizes 2 <= L <= 64: GCC 11
+// The reference's k-way merge of ONE target by ONE WAVEFRONT (:743-800), list sizes 2 <= L <= 64 R: GCC 11
 // bits/stl_heap.h -- make_heap, then pop_heap with __adjust_heap and __push_heap -- and the fingerprint
 // de-duplication, restated on lane-resident values.  Everything the merge decides on is wavefront-uniform and lives in
-// registers spread over the lanes -- heap element e in lane e, accepted entry a in lane a -- read with v_readlane and
-// written with a lane select: a few cycles per access; the scan over the accepted fingerprints is ONE ballot instead
-// of a loop over L entries.  The caller holds the candidates, entry j of list i (i, j wavefront-uniform):
+// registers spread over the lanes -- heap element e in lane e, accepted entry a in lane a & 63 of register row a >> 6
+// (R rows; R = 1: lane a) -- read with v_readlane and written with a lane select: a few cycles per access; the scan over
+// the accepted fingerprints is ONE ballot per row, rows in ascending order, instead of a loop over L entries.  The heap
+// never holds more than one element per candidate list (8), whatever L.
+// The caller holds the candidates, entry j of list i (i, j wavefront-uniform):
 //   score(i, j)     its score (-inf: no such entry; j < L),    fp(i, j)  its fingerprint with the step's delta applied
 //   word(i, j, w)   word w (per lane) of its message as it would stand in the target
 // addv: transition score of list i in lane i; Wd: message words in use at the target.  All 64 lanes must be active.
-// Returns the number l of accepted entries; entry a < l in lane a: score as, fingerprint ay, source ax = i << 16 | j.
+// Returns the number l of accepted entries; entry a < l in lane a & 63 of row a >> 6: score as, fingerprint ay, source
+// ax = i << 16 | j.
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ float lane_f(float v, uint32_t ln) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int)ln)); }
 __device__ __forceinline__ uint32_t lane_u(uint32_t v, uint32_t ln) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)ln); }
 
-template <typename ScoreF, typename FpF, typename WordF>
+// The rows of a wavefront's registers are written out below (if constexpr), not looped over: a loop over a register array is
+// taken apart late by the compiler, and the one-row instances would no longer be the code they were before there were rows.
+
+// entry held by `lane` in row r
+template <int R> __device__ __forceinline__ uint32_t row_entry(uint32_t lane, uint32_t r) { return R == 1 ? lane : lane + 64u * r; }
+
+// :778-779 over one row of accepted entries: is candidate (i, j) the message of one of the entries in `match` (lanes whose
+// fingerprint equals the candidate's; axr: their sources)?  dup: already found in an earlier row.
+template <typename WordF>
+__device__ __forceinline__ bool same_message(unsigned long long match, uint32_t axr, uint32_t i, uint32_t j, uint32_t lane, uint32_t Wd,
+                                             WordF& word, bool dup) {
+  while (match && !dup) {
+    const uint32_t a = (uint32_t)__builtin_ctzll(match);
+    match &= match - 1;
+    const uint32_t asrc = lane_u(axr, a);
+    const uint32_t w = lane < Wd ? lane : 0u;                          // (every lane loads: no per-lane branch in front of word's loads)
+    const uint32_t diff = word(i, j, w) ^ word(asrc >> 16, asrc & 0xFFFFu, w);
+    dup = __ballot(lane < Wd && diff != 0) == 0ull;
+  }
+  return dup;
+}
+// does candidate register u = i' R + r' hold entry j of list i?  (one row: i alone picks it)
+template <int R> __device__ __forceinline__ bool row_holds(uint32_t u, uint32_t i, uint32_t j) {
+  return R == 1 ? i == u : (i == u / R && (j >> 6) == u % R);
+}
+
+template <int R, typename ScoreF, typename FpF, typename WordF>
 __device__ __forceinline__ uint32_t wave_merge(uint32_t L, uint32_t nlists, uint32_t Wd, uint32_t lane, float addv, ScoreF score,
-                                               FpF fp, WordF word, float& as, uint32_t& ay, uint32_t& ax) {
+                                               FpF fp, WordF word, float (&as)[R], uint32_t (&ay)[R], uint32_t (&ax)[R]) {
   const float NEG = -INFINITY;
   auto wrf = [lane](float& v, uint32_t ln, float x) { v = lane == ln ? x : v; };          // (clang 22 has no writelane builtin)
   auto wru = [lane](uint32_t& v, uint32_t ln, uint32_t x) { v = lane == ln ? x : v; };
   float hs = NEG; uint32_t hx = 0;                          // heap element e in lane e: score, (list << 16 | index in list)
-  as = NEG; ay = 0; ax = 0;
+  as[0] = NEG; ay[0] = 0; ax[0] = 0;
+  if constexpr (R > 1) { as[1] = NEG; ay[1] = 0; ax[1] = 0; }
+  if constexpr (R > 2) { as[2] = NEG; ay[2] = 0; ax[2] = 0; }
+  if constexpr (R > 3) { as[3] = NEG; ay[3] = 0; ax[3] = 0; }
   auto sift_up = [&](uint32_t hole, uint32_t top, float vs, uint32_t vx) {
     while (hole > top) {
       const uint32_t parent = (hole - 1) / 2;
@@ -582,16 +616,19 @@ __device__ __forceinline__ uint32_t wave_merge(uint32_t L, uint32_t nlists, uint
     const uint32_t i = tx >> 16, j = tx & 0xFFFFu;
     const uint32_t ch = fp(i, j);
     bool dup = false;                                                  // :778-779
-    unsigned long long match = __ballot(lane < l && ay == ch);        // different fingerprint => different message
-    while (match && !dup) {
-      const uint32_t a = (uint32_t)__builtin_ctzll(match);
-      match &= match - 1;
-      const uint32_t asrc = lane_u(ax, a);
-      const uint32_t w = lane < Wd ? lane : 0u;                        // (every lane loads: no per-lane branch in front of word's loads)
-      const uint32_t diff = word(i, j, w) ^ word(asrc >> 16, asrc & 0xFFFFu, w);
-      dup = __ballot(lane < Wd && diff != 0) == 0ull;
+    // different fingerprint => different message; accepted entries in ascending order, 64 per row
+    dup = same_message(__ballot(row_entry<R>(lane, 0) < l && ay[0] == ch), ax[0], i, j, lane, Wd, word, dup);
+    if constexpr (R > 1) dup = same_message(__ballot(row_entry<R>(lane, 1) < l && ay[1] == ch), ax[1], i, j, lane, Wd, word, dup);
+    if constexpr (R > 2) dup = same_message(__ballot(row_entry<R>(lane, 2) < l && ay[2] == ch), ax[2], i, j, lane, Wd, word, dup);
+    if constexpr (R > 3) dup = same_message(__ballot(row_entry<R>(lane, 3) < l && ay[3] == ch), ax[3], i, j, lane, Wd, word, dup);
+    if (!dup) {                                                        // :780-783
+      const uint32_t ln = R == 1 ? l : l & 63u, row = R == 1 ? 0u : l >> 6;
+      if (row == 0) { wrf(as[0], ln, ts); wru(ay[0], ln, ch); wru(ax[0], ln, tx); }
+      if constexpr (R > 1) if (row == 1) { wrf(as[1], ln, ts); wru(ay[1], ln, ch); wru(ax[1], ln, tx); }
+      if constexpr (R > 2) if (row == 2) { wrf(as[2], ln, ts); wru(ay[2], ln, ch); wru(ax[2], ln, tx); }
+      if constexpr (R > 3) if (row == 3) { wrf(as[3], ln, ts); wru(ay[3], ln, ch); wru(ax[3], ln, tx); }
+      ++l;
     }
-    if (!dup) { wrf(as, l, ts); wru(ay, l, ch); wru(ax, l, tx); ++l; }   // :780-783
     if (j == L - 1) continue;                                          // :788
     const float nxt = score(i, j + 1);
     if (nxt != NEG) {                                                  // :790-796
@@ -638,68 +675,19 @@ __device__ __forceinline__ void for_each_fixup_target(const StepArgs& args, cons
   }
 }
 
-// ---------------------------------------------------------------------------------------
-// The literal reference merge of ONE target by ONE WAVEFRONT (wave_merge), list sizes 2 <= L <= 64, either layout.
-// Lane j holds entry j of each of the target's <= 8 candidate lists (8 registers); all loads/stores of list entries
-// are spread over the lanes.
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ void wave_target(const Geometry& g, const SlotStep& ss, const uint32_t* __restrict__ prev,
-                                            uint32_t* __restrict__ cur, const Target& tg, uint32_t pos, uint32_t lane) {
-  const uint32_t k = tg.k;
-  const uint32_t L = g.L, sBlk = g.sBlk, sCrf = (uint32_t)g.sCrf;
-  const uint32_t Wd = 2 * tg.np_dst;
-  const float NEG = -INFINITY;
-  const uint32_t own_sh = rec_sh(g, tg.own, tg.c, 0, tg.np_dst);
-  if (pos == 0) {                                                      // :706-713
-    if (lane == 0) {
-      cur[own_sh] = f2u(u2f(prev[own_sh]) + ss.post_row[tg.row * 8 + k]);
-      cur[own_sh + 1] = prev[own_sh + 1];
-    }
-    if (lane < Wd) cur[rec_word(g, tg.own, tg.c, 0, lane, tg.np_dst)] = prev[rec_word(g, tg.own, tg.c, 0, lane, tg.np_dst)];
-    if (lane >= 1 && lane < L) cur[rec_sh(g, tg.own, tg.c, lane, tg.np_dst)] = kNegInfBits;
-    return;
-  }
-  // 1. candidates: register i of lane j = entry j of list i (score, fingerprint with the step's delta applied)
-  float cs[8]; uint32_t cy[8];
-#pragma unroll
-  for (uint32_t i = 0; i < 8; ++i) {
-    cs[i] = NEG; cy[i] = 0;
-    if (i < tg.nlists && ((tg.okmask >> i) & 1u) && lane < L) {
-      const uint32_t b = rec_sh(g, i == 0 ? tg.own : tg.src + (list_crf(k, i) >> tg.csrc) * sCrf, i == 0 ? tg.c : tg.cp, lane, i == 0 ? tg.np_dst : tg.np_src);
-      const uint2 v = *reinterpret_cast<const uint2*>(prev + b);
-      cs[i] = u2f(v.x); cy[i] = i != 0 ? v.y ^ tg.fpc : v.y;
-    }
-  }
-  auto cand_s = [&](uint32_t i, uint32_t j) -> float {      // i, j wavefront-uniform
-    float v = opq(cs[0]);                                   // (opaque copies: a plain select chain is folded into an indexed
-#pragma unroll                                              //  load and the array then lives in scratch memory)
-    for (uint32_t u = 1; u < 8; ++u) v = i == u ? opq(cs[u]) : v;
-    return lane_f(v, j);
-  };
-  auto cand_y = [&](uint32_t i, uint32_t j) -> uint32_t {
-    uint32_t v = opq(cy[0]);
-#pragma unroll
-    for (uint32_t u = 1; u < 8; ++u) v = i == u ? opq(cy[u]) : v;
-    return lane_u(v, j);
-  };
-  float addv = 0.0f;                                        // transition score of list i in lane i
-  if (lane < tg.nlists) addv = ss.post_row[tg.row * 8 + (lane == 0 ? k : list_crf(k, lane))];
-  // word w of the candidate message built from entry (li, lj): per-lane arguments allowed
-  auto word_of = [&](uint32_t li, uint32_t lj, uint32_t w) -> uint32_t {
-    const uint32_t lst = li == 0 ? tg.own : tg.src + (list_crf(k, li) >> tg.csrc) * sCrf;
-    const uint32_t cv = li == 0 ? tg.c : tg.cp, np = li == 0 ? tg.np_dst : tg.np_src;
-    const uint32_t v = entry_word(g, prev, lst, cv, lj, w, np);
-    if (li == 0) return v;
-    const uint32_t lowpart = w == 0 ? tg.newbits : (entry_word(g, prev, lst, cv, lj, w - 1, np) >> (32 - tg.shift));
-    return (v << tg.shift) | lowpart;
-  };
-  // 2. the reference merge (:743-800)
-  float as; uint32_t ay, ax;
-  const uint32_t l = wave_merge(L, tg.nlists, Wd, lane, addv, cand_s, cand_y, word_of, as, ay, ax);
-  // 3. outputs: lane a writes list entry a (:781, :799) and, if accepted, its message
-  if (lane < L) {
-    *reinterpret_cast<uint2*>(cur + rec_sh(g, tg.own, tg.c, lane, tg.np_dst)) = lane < l ? make_uint2(f2u(as), ay) : make_uint2(kNegInfBits, 0u);
-    if (lane < l) {          // the whole message in the widest pieces the layout has (not word by word: every access of a lane is its own line)
+// Position 0 (:706-713): entries 1 .. L-1 of the target's list are empty -- entry e, one per lane.
+__device__ __forceinline__ void wave_clear_entry(const Geometry& g, uint32_t* __restrict__ cur, const Target& tg, uint32_t e) {
+  if (e >= 1 && e < g.L) cur[rec_sh(g, tg.own, tg.c, e, tg.np_dst)] = kNegInfBits;
+}
+
+// Output of wave_target, entry e of the target's list, one per lane (:781, :799): the l accepted entries -- score as, fingerprint
+// ay, taken from ax = list << 16 | index in list -- with their messages, -inf behind them.
+__device__ __forceinline__ void wave_output_entry(const Geometry& g, const uint32_t* __restrict__ prev, uint32_t* __restrict__ cur,
+                                                  const Target& tg, uint32_t e, uint32_t l, float as, uint32_t ay, uint32_t ax) {
+  const uint32_t k = tg.k, sBlk = g.sBlk, sCrf = (uint32_t)g.sCrf;
+  if (e < g.L) {
+    *reinterpret_cast<uint2*>(cur + rec_sh(g, tg.own, tg.c, e, tg.np_dst)) = e < l ? make_uint2(f2u(as), ay) : make_uint2(kNegInfBits, 0u);
+    if (e < l) {             // the whole message in the widest pieces the layout has (not word by word: every access of a lane is its own line)
       const uint32_t li = ax >> 16, lj = ax & 0xFFFFu;
       const uint32_t lst = li == 0 ? tg.own : tg.src + (list_crf(k, li) >> tg.csrc) * sCrf, cv = li == 0 ? tg.c : tg.cp;
       uint32_t m[8];
@@ -713,24 +701,128 @@ __device__ __forceinline__ void wave_target(const Geometry& g, const SlotStep& s
           m[2 * q2] = v.x; m[2 * q2 + 1] = v.y;
         }
         push_bits<8>(m, li == 0 ? 0u : tg.shift, tg.newbits);
-        uint32_t* wp = cur + rec_sh(g, tg.own, tg.c, lane, tg.np_dst) + 2;
+        uint32_t* wp = cur + rec_sh(g, tg.own, tg.c, e, tg.np_dst) + 2;
 #pragma unroll
         for (uint32_t q2 = 0; q2 < 4; ++q2)
           if (q2 < tg.np_dst) *reinterpret_cast<lva_u32x2*>(wp + 2 * q2) = lva_u32x2{m[2 * q2], m[2 * q2 + 1]};
       } else {
         load_msg<4>(prev + lst + lj * sBlk + 2 * g.N, g.N, cv, li == 0 ? tg.np_dst : tg.np_src, m);
         push_bits<8>(m, li == 0 ? 0u : tg.shift, tg.newbits);
-        store_msg<4>(cur + tg.own + lane * sBlk + 2 * g.N, g.N, tg.c, tg.np_dst, m);
+        store_msg<4>(cur + tg.own + e * sBlk + 2 * g.N, g.N, tg.c, tg.np_dst, m);
       }
     }
   }
 }
-}  // namespace
 
-// wave kernel: wave_target over the whole step -- kernel mode 3.
-// grid: x = groups of 4 conv states, y = band position index * 8 + crf state, z = slot.
-__global__ __launch_bounds__(256) void lva_step_wave(StepArgs args, Geometry g, const DevCode* __restrict__ codes,
-                                                     uint32_t* __restrict__ trellis) {
+// ---------------------------------------------------------------------------------------
+// The literal reference merge of ONE target by ONE WAVEFRONT (wave_merge), list sizes 2 <= L <= 64 R, either layout.
+// Entry j of each of the target's <= 8 candidate lists sits in lane j & 63 of register row j >> 6 (8 R registers of
+// scores, 8 R of fingerprints; R = 1: lane j holds entry j); all loads/stores of list entries are spread over the lanes,
+// one row -- 64 consecutive entries of a list -- per request.
+// ---------------------------------------------------------------------------------------
+template <int R>
+__device__ __forceinline__ void wave_target(const Geometry& g, const SlotStep& ss, const uint32_t* __restrict__ prev,
+                                            uint32_t* __restrict__ cur, const Target& tg, uint32_t pos, uint32_t lane) {
+  const uint32_t k = tg.k;
+  const uint32_t L = g.L, sBlk = g.sBlk, sCrf = (uint32_t)g.sCrf;
+  const uint32_t Wd = 2 * tg.np_dst;
+  const float NEG = -INFINITY;
+  const uint32_t own_sh = rec_sh(g, tg.own, tg.c, 0, tg.np_dst);
+  if (pos == 0) {                                                      // :706-713
+    if (lane == 0) {
+      cur[own_sh] = f2u(u2f(prev[own_sh]) + ss.post_row[tg.row * 8 + k]);
+      cur[own_sh + 1] = prev[own_sh + 1];
+    }
+    if (lane < Wd) cur[rec_word(g, tg.own, tg.c, 0, lane, tg.np_dst)] = prev[rec_word(g, tg.own, tg.c, 0, lane, tg.np_dst)];
+    wave_clear_entry(g, cur, tg, row_entry<R>(lane, 0));
+    if constexpr (R > 1) wave_clear_entry(g, cur, tg, row_entry<R>(lane, 1));
+    if constexpr (R > 2) wave_clear_entry(g, cur, tg, row_entry<R>(lane, 2));
+    if constexpr (R > 3) wave_clear_entry(g, cur, tg, row_entry<R>(lane, 3));
+    return;
+  }
+  // 1. candidates: register (i, r) of lane j = entry 64 r + j of list i (score, fingerprint with the step's delta applied).
+  // Straight-line code: all 8 R requests leave before the first value is used.
+  float cs[8 * R]; uint32_t cy[8 * R];                      // register u = i R + r
+  if constexpr (R == 1) {
+#pragma unroll
+    for (uint32_t i = 0; i < 8; ++i) {
+      cs[i] = NEG; cy[i] = 0;
+      if (i < tg.nlists && ((tg.okmask >> i) & 1u) && lane < L) {
+        const uint32_t b = rec_sh(g, i == 0 ? tg.own : tg.src + (list_crf(k, i) >> tg.csrc) * sCrf, i == 0 ? tg.c : tg.cp, lane, i == 0 ? tg.np_dst : tg.np_src);
+        const uint2 v = *reinterpret_cast<const uint2*>(prev + b);
+        cs[i] = u2f(v.x); cy[i] = i != 0 ? v.y ^ tg.fpc : v.y;
+      }
+    }
+  } else {
+    // Rows: the 8 R requests, 64 consecutive entries of a list each, leave back to back -- no branch between them, per lane or
+    // uniform (loads behind branches are compiled as load, wait, next).  A list that does not exist reads the target's own list in
+    // its place, a lane beyond the list's end reads entry L - 1: memory of this slot in either case, and the value is dropped.
+    // The six lists only a flip target has are one uniform branch as a whole.
+    uint32_t ec[R];
+#pragma unroll
+    for (uint32_t r = 0; r < R; ++r) ec[r] = min(row_entry<R>(lane, r), L - 1);
+    lva_u32x2 v[8 * R];
+    auto request = [&](uint32_t i) __attribute__((always_inline)) {
+      const bool have = (tg.okmask >> i) & 1u, own = i == 0 || !have;
+      const uint32_t lst = own ? tg.own : tg.src + (list_crf(k, i) >> tg.csrc) * sCrf, np = own ? tg.np_dst : tg.np_src;
+      const uint32_t base = rec_sh(g, lst, own ? tg.c : tg.cp, 0, np), stride = g.rec ? 2u + 2u * np : sBlk;   // rec_sh is linear in the entry
+#pragma unroll
+      for (uint32_t r = 0; r < R; ++r) v[i * R + r] = *LVA_GLOBAL(lva_u32x2, prev + base + ec[r] * stride);
+    };
+    request(0); request(1);
+    if (tg.nlists == 8) {
+#pragma unroll
+      for (uint32_t i = 2; i < 8; ++i) request(i);
+    } else {
+#pragma unroll
+      for (uint32_t u = 2 * R; u < 8 * R; ++u) v[u] = lva_u32x2{kNegInfBits, 0u};
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < 8 * R; ++u) {
+      const uint32_t i = u / R;
+      const bool have = i < tg.nlists && ((tg.okmask >> i) & 1u) && row_entry<R>(lane, u % R) < L;
+      cs[u] = have ? u2f(v[u].x) : NEG;
+      cy[u] = have ? (i != 0 ? v[u].y ^ tg.fpc : v[u].y) : 0u;
+    }
+  }
+  auto cand_s = [&](uint32_t i, uint32_t j) -> float {      // i, j wavefront-uniform
+    float v = opq(cs[0]);                                   // (opaque copies: a plain select chain is folded into an indexed
+#pragma unroll                                              //  load and the array then lives in scratch memory)
+    for (uint32_t u = 1; u < 8 * R; ++u) v = row_holds<R>(u, i, j) ? opq(cs[u]) : v;
+    return lane_f(v, R == 1 ? j : j & 63u);
+  };
+  auto cand_y = [&](uint32_t i, uint32_t j) -> uint32_t {
+    uint32_t v = opq(cy[0]);
+#pragma unroll
+    for (uint32_t u = 1; u < 8 * R; ++u) v = row_holds<R>(u, i, j) ? opq(cy[u]) : v;
+    return lane_u(v, R == 1 ? j : j & 63u);
+  };
+  float addv = 0.0f;                                        // transition score of list i in lane i
+  if (lane < tg.nlists) addv = ss.post_row[tg.row * 8 + (lane == 0 ? k : list_crf(k, lane))];
+  // word w of the candidate message built from entry (li, lj): per-lane arguments allowed
+  auto word_of = [&](uint32_t li, uint32_t lj, uint32_t w) -> uint32_t {
+    const uint32_t lst = li == 0 ? tg.own : tg.src + (list_crf(k, li) >> tg.csrc) * sCrf;
+    const uint32_t cv = li == 0 ? tg.c : tg.cp, np = li == 0 ? tg.np_dst : tg.np_src;
+    const uint32_t v = entry_word(g, prev, lst, cv, lj, w, np);
+    if (li == 0) return v;
+    const uint32_t lowpart = w == 0 ? tg.newbits : (entry_word(g, prev, lst, cv, lj, w - 1, np) >> (32 - tg.shift));
+    return (v << tg.shift) | lowpart;
+  };
+  // 2. the reference merge (:743-800)
+  float as[R]; uint32_t ay[R], ax[R];
+  const uint32_t l = wave_merge<R>(L, tg.nlists, Wd, lane, addv, cand_s, cand_y, word_of, as, ay, ax);
+  // 3. outputs: lane a & 63 writes list entry a of row a >> 6
+  wave_output_entry(g, prev, cur, tg, row_entry<R>(lane, 0), l, as[0], ay[0], ax[0]);
+  if constexpr (R > 1) wave_output_entry(g, prev, cur, tg, row_entry<R>(lane, 1), l, as[1], ay[1], ax[1]);
+  if constexpr (R > 2) wave_output_entry(g, prev, cur, tg, row_entry<R>(lane, 2), l, as[2], ay[2], ax[2]);
+  if constexpr (R > 3) wave_output_entry(g, prev, cur, tg, row_entry<R>(lane, 3), l, as[3], ay[3], ax[3]);
+}
+
+// wave_target on one workgroup of the whole-step grid (lva_step_wave, lva_step_wave_wide): x = groups of 4 conv states,
+// y = band position index * 8 + crf state, z = slot; 256 threads, one wavefront per target.
+template <int R>
+__device__ __forceinline__ void wave_step(const StepArgs& args, const Geometry& g, const DevCode* __restrict__ codes,
+                                          uint32_t* __restrict__ trellis) {
   SlotStep ss;
   if (!load_slot(args, blockIdx.z, &ss)) return;
   const uint32_t pos = ss.lo + (blockIdx.y >> 3), k = blockIdx.y & 7u;
@@ -742,7 +834,25 @@ __global__ __launch_bounds__(256) void lva_step_wave(StepArgs args, Geometry g, 
   slot_buffers(ss, g, trellis, &prev, &cur);
   Target tg;
   if (!resolve_target(cd, g, ss, pos, c, k, &tg)) return;              // (uniform per wavefront)
-  wave_target(g, ss, prev, cur, tg, pos, threadIdx.x & 63u);
+  wave_target<R>(g, ss, prev, cur, tg, pos, threadIdx.x & 63u);
+}
+}  // namespace
+
+// wave kernel: wave_target over the whole step -- kernel mode 3.
+// grid: x = groups of 4 conv states, y = band position index * 8 + crf state, z = slot.
+__global__ __launch_bounds__(256) void lva_step_wave(StepArgs args, Geometry g, const DevCode* __restrict__ codes,
+                                                     uint32_t* __restrict__ trellis) {
+  wave_step<1>(args, g, codes, trellis);
+}
+
+// wide wave kernel: the same for lists of 65..256 entries, R = ceil(L / 64) register rows per candidate list and for the
+// accepted entries (wave_target<R>) -- kernel mode 3 above 64 entries.  16 R + 3 R registers on top of the narrow kernel's:
+// held to 128 (four wavefronts per SIMD), no scratch memory.
+template <int R>
+__global__ __launch_bounds__(256, 4) void lva_step_wave_wide(StepArgs args, Geometry g, const DevCode* __restrict__ codes,
+                                                             uint32_t* __restrict__ trellis) {
+  static_assert(R >= 2 && R <= 4, "lists of 65..256 entries");
+  wave_step<R>(args, g, codes, trellis);
 }
 
 // fix-up pass behind lva_step_fast (L = 2/4/8) and the big-list fast kernels (8 < L <= 64, and list sizes that are not a
@@ -753,7 +863,7 @@ __global__ __launch_bounds__(256, 8) void lva_step_fixup_wave(StepArgs args, Geo
   const uint32_t lane = threadIdx.x & 63u;
   for_each_fixup_target(args, g, codes, trellis, hdr, items,
                         [&](const DevCode&, const SlotStep& ss, const uint32_t* prev, uint32_t* cur, const Target& tg, uint32_t pos) {
-                          wave_target(g, ss, prev, cur, tg, pos, lane);
+                          wave_target<1>(g, ss, prev, cur, tg, pos, lane);
                         });
 }
 
@@ -1596,14 +1706,14 @@ __global__ __launch_bounds__(256) void lva_step_fixup_lazy(StepArgs args, Geomet
     };
     // 2. the reference merge (:743-800)
     const uint32_t Wd = 2 * tg.np_dst;
-    float as; uint32_t ay, ax;
-    const uint32_t l = wave_merge(L, tg.nlists, Wd, lane, addv, [&](uint32_t i, uint32_t j) { return lane_f(cs, i * 8 + j); },
+    float as[1]; uint32_t ay[1], ax[1];
+    const uint32_t l = wave_merge<1>(L, tg.nlists, Wd, lane, addv, [&](uint32_t i, uint32_t j) { return lane_f(cs, i * 8 + j); },
                                   [&](uint32_t i, uint32_t j) { return lane_u(cy, i * 8 + j); }, word_of, as, ay, ax);
     // 3. outputs: lane = entry*8 + word
     {
       const uint32_t e = lane >> 3, w = lane & 7u;
-      const float es = __shfl(as, (int)e);
-      const uint32_t ey = __shfl(ay, (int)e), ex = __shfl(ax, (int)e);
+      const float es = __shfl(as[0], (int)e);
+      const uint32_t ey = __shfl(ay[0], (int)e), ex = __shfl(ax[0], (int)e);
       if (e < L && w == 0)
         *reinterpret_cast<uint2*>(cur + tg.own + e * sBlk + 2 * tg.c) = e < l ? make_uint2(f2u(es), ey) : make_uint2(kNegInfBits, 0u);
       const uint32_t li = (ex >> 16) & 7u, lj = ex & 7u;
@@ -2370,22 +2480,6 @@ int launch_step_exact(const StepArgs& a, const Geometry& g, const DevCode* codes
   return (int)hipGetLastError();
 }
 
-int launch_step_wave(const StepArgs& a, const Geometry& g, const DevCode* codes, uint32_t* trellis, void* stream) {
-  if (a.nslots == 0 || a.band_max == 0) return 0;
-  dim3 grid((g.N + 3) / 4, a.band_max * 8, a.nslots), block(256);
-  hipLaunchKernelGGL(lva_step_wave, grid, block, 0, (hipStream_t)stream, a, g, codes, trellis);
-  return (int)hipGetLastError();
-}
-
-bool wave_kernel_available(const Geometry& g) { return g.L >= 2 && g.L <= 64; }
-
-static bool small_list(const Geometry& g) { return g.L == 1 || g.L == 2 || g.L == 4 || g.L == 8; }
-
-bool fast_kernel_available(const Geometry& g) {
-  const bool l_ok = small_list(g) || (g.L >= 2 && g.L <= 64);
-  return l_ok && g.P >= 1 && g.P <= 4 && g.N >= 64;
-}
-
 // f(std::integral_constant<int, V>{}) for the V of Vs that equals the run-time value v (a list size, a message plane count):
 // f's result, or hipErrorInvalidValue when v is none of them
 template <int... Vs, typename F>
@@ -2393,6 +2487,29 @@ static int with_constant(uint32_t v, F&& f) {
   int e = (int)hipErrorInvalidValue;
   ((v == (uint32_t)Vs ? (void)(e = f(std::integral_constant<int, Vs>{})) : (void)0), ...);
   return e;
+}
+
+int launch_step_wave(const StepArgs& a, const Geometry& g, const DevCode* codes, uint32_t* trellis, void* stream) {
+  if (a.nslots == 0 || a.band_max == 0) return 0;
+  dim3 grid((g.N + 3) / 4, a.band_max * 8, a.nslots), block(256);
+  if (g.L <= 64) {
+    hipLaunchKernelGGL(lva_step_wave, grid, block, 0, (hipStream_t)stream, a, g, codes, trellis);
+    return (int)hipGetLastError();
+  }
+  return with_constant<2, 3, 4>((g.L + 63) / 64, [&](auto r) {       // register rows of 64 entries
+    hipLaunchKernelGGL((lva_step_wave_wide<decltype(r)::value>), grid, block, 0, (hipStream_t)stream, a, g, codes, trellis);
+    return (int)hipGetLastError();
+  });
+}
+
+bool wave_kernel_available(const Geometry& g) { return g.L >= 2 && g.L <= 64; }
+bool wave_wide_kernel_available(const Geometry& g) { return g.L > 64 && g.L <= 256; }
+
+static bool small_list(const Geometry& g) { return g.L == 1 || g.L == 2 || g.L == 4 || g.L == 8; }
+
+bool fast_kernel_available(const Geometry& g) {
+  const bool l_ok = small_list(g) || (g.L >= 2 && g.L <= 64);
+  return l_ok && g.P >= 1 && g.P <= 4 && g.N >= 64;
 }
 
 int launch_step_fast(const StepArgs& a, const Geometry& g, const DevCode* codes, uint32_t* trellis, WorkHdr* hdr,

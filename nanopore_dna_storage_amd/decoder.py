@@ -117,7 +117,8 @@ class Decoder:
 
     kernel: 0 = default (the fastest mode for the configuration: 4 for list sizes 2 / 4 / 8 with up to 192 message bits,
     else 2 for list sizes up to 64, the thread-per-target exact kernel beyond), 1 = thread-per-target exact kernel,
-    2 = fast kernel + exact fix-up, 3 = wavefront-per-target exact kernel, 4 = fast kernel with lazy messages
+    2 = fast kernel + exact fix-up, 3 = wavefront-per-target exact kernel (list sizes 2..256; above 64 entries it is the one
+    alternative to mode 1 and has to be asked for), 4 = fast kernel with lazy messages
     (materialised every second time step).  All modes give the reference's lists bit for bit; they differ in speed only."""
 
     def __init__(self, mem_conv, rate, msg_len, list_size=1, max_deviation=None, sync_marker="", sync_period=0,
