@@ -105,7 +105,8 @@ typedef struct lva_profile {
  * every JSON line; profiles/ *_traffic.json carry it). */
 const char *lva_version(void);
 /* LVA_ABI_VERSION of the library that was loaded.  It changes whenever a struct of this header changes size or layout
- * (5: lva_profile gained overflow_steps and working_bytes): a caller built against another value must not pass structs. */
+ * (5: lva_profile gained overflow_steps and working_bytes): a caller built against another value must not pass structs.
+ * Entry points added since (lva_stream_*, lva_transpost_*, lva_device_download) change no struct and keep it at 5. */
 #define LVA_ABI_VERSION 5
 int lva_abi_version(void);
 const char *lva_strerror(int code);
@@ -219,6 +220,35 @@ int lva_device_alloc(lva_decoder *d, uint64_t bytes, void **out_dev_ptr);
 int lva_device_free(lva_decoder *d, void *dev_ptr);
 int lva_device_upload(lva_decoder *d, void *dev_dst, const void *host_src, uint64_t bytes);
 int lva_device_synchronize(lva_decoder *d);
+/* The counterpart of lva_device_upload: device -> host on the decoder's stream, complete on return. */
+int lva_device_download(lva_decoder *d, void *host_dst, const void *dev_src, uint64_t bytes);
+
+/* ---------------------------------------------------------------------------------------------
+ * transition posteriors of a flip-flop CRF from the network's raw transition
+ * scores, so that the chain on the device starts where a network ends:
+ * scores -> posteriors -> basecall -> barcode -> window -> lists.
+ * scores: float32 [blocks][40] per read, reads back to back with row_offsets[n_reads+1] as for lva_decode_batch
+ * (row_offsets[0] = 0), in the layout of flappie's `trans` matrix and of .post: [b*8+s] = score of entering
+ * flip base b from state s, [32+s] = score of entering flop (from flip s for s < 4, staying in flop s otherwise).
+ * The output has the same shape and holds log-posteriors: the log-sum-exp of every block is 0.  Forward and
+ * backward vectors start at 0 for all 8 states (decode.c:386, :425).  fp32, in an order of the library's own (the
+ * values agree with a float64 forward-backward to a few 1e-6; flappie's own float32 chain is further from it).
+ * Non-finite scores give what IEEE arithmetic gives for that read; other reads are unaffected.  A read may have
+ * no block.  Limits as for the basecall entry points below: 2^20 blocks per read, fewer than 2^31 per batch,
+ * otherwise LVA_ERR_ARG (decided from the offsets, before anything is allocated).  Device buffers are 16-byte
+ * aligned.  Both calls run on the decoder's stream and are complete on return; LVA_ERR_BUSY while a decode stream
+ * is open.  Afterwards lva_decoder_profile reports total_ms = HIP-event time of the two kernels and read_steps =
+ * blocks of the batch (slots and kernel as before, everything else 0).
+ * ------------------------------------------------------------------------------------------- */
+
+/* replaces: transpost_crf_flipflop(trans, true) (flappie/src/decode.c:377-497) + log_row_normalise_inplace
+ * (flappie/src/flappie_matrix.c:450-467) */
+int lva_transpost_batch(lva_decoder *d, const float *scores, const int64_t *row_offsets, int32_t n_reads, float *post_out);
+/* Same with the scores resident on the decoder's device.  post_dev may equal scores_dev (in place); otherwise the two
+ * must not overlap.  The result is what lva_basecall_batch_device, lva_locate_payload_batch_device,
+ * lva_decode_batch_device and lva_decode_windows_device take: no copy in between. */
+int lva_transpost_batch_device(lva_decoder *d, const float *scores_dev, const int64_t *row_offsets, int32_t n_reads,
+                               float *post_dev /* may equal scores_dev */);
 
 /* ---------------------------------------------------------------------------------------------
  * the step in front of the list decoder on real data -- flappie's

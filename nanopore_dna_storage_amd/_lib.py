@@ -27,6 +27,7 @@ EXPORTS = [
     "lva_locate_payload_batch", "lva_locate_payload_batch_device",
     "lva_rs_decode", "lva_rs_encode", "lva_rs_last_error",
     "lva_stream_open", "lva_stream_close", "lva_stream_submit", "lva_stream_poll", "lva_stream_pending",
+    "lva_transpost_batch", "lva_transpost_batch_device", "lva_device_download",
 ]
 
 
@@ -144,5 +145,11 @@ def load_library():
     L.lva_stream_submit.argtypes = [vp, vp, i64, i32, u64]
     L.lva_stream_poll.argtypes = [vp, i32, i32, vp, vp, vp, vp, ctypes.POINTER(i32)]
     L.lva_stream_pending.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    for name in ("lva_transpost_batch", "lva_transpost_batch_device", "lva_device_download"):
+        if not hasattr(L, name):                     # additive as the stream was: same ABI version
+            raise ImportError("%s has no transition posteriors (%s): rebuild it" % (path, name))
+    L.lva_transpost_batch.argtypes = [vp, vp, vp, i32, vp]
+    L.lva_transpost_batch_device.argtypes = [vp, vp, vp, i32, vp]
+    L.lva_device_download.argtypes = [vp, vp, vp, u64]
     _lib = L
     return L

@@ -24,6 +24,7 @@
 #include "lva_device.h"
 #include "lva_kernels.h"
 #include "bc_kernels.h"
+#include "tp_kernels.h"
 
 using namespace lva;
 
@@ -72,6 +73,10 @@ struct lva_decoder {
   std::vector<hipEvent_t> ev_pool;
   lva_profile prof{};
   lva_stream* open_stream = nullptr;   // lva_stream_open .. lva_stream_close: the batch entry points refuse meanwhile
+  float* d_tp_fwd = nullptr;   // lva_transpost_*: forward vectors, 8 floats per block; grows, never shrinks
+  size_t tp_fwd_cap = 0;       // blocks
+  int64_t* d_tp_off = nullptr; // lva_transpost_*: row offsets of the batch
+  size_t tp_off_cap = 0;       // entries
 };
 
 namespace {
@@ -400,6 +405,8 @@ void lva_decoder_destroy(lva_decoder* d) {
   if (d->d_slots) (void)hipFree(d->d_slots);
   if (d->d_steps) (void)hipFree(d->d_steps);
   if (d->d_band) (void)hipFree(d->d_band);
+  if (d->d_tp_fwd) (void)hipFree(d->d_tp_fwd);
+  if (d->d_tp_off) (void)hipFree(d->d_tp_off);
   for (hipEvent_t e : d->ev_pool) (void)hipEventDestroy(e);
   if (d->ev_h2d) (void)hipEventDestroy(d->ev_h2d);
   if (d->d_codes) (void)hipFree(d->d_codes);
@@ -1087,6 +1094,14 @@ int lva_device_upload(lva_decoder* d, void* dev_dst, const void* host_src, uint6
   return LVA_OK;
 }
 
+int lva_device_download(lva_decoder* d, void* host_dst, const void* dev_src, uint64_t bytes) {
+  if (!d || (bytes && (!host_dst || !dev_src))) return LVA_ERR_ARG;
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipMemcpyAsync(host_dst, dev_src, (size_t)bytes, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  return LVA_OK;
+}
+
 int lva_device_synchronize(lva_decoder* d) {
   if (!d) return LVA_ERR_ARG;
   HIP_TRY(hipSetDevice(d->device));
@@ -1245,6 +1260,107 @@ int lva_locate_payload_batch(lva_decoder* d, const float* post, const int64_t* r
   st = upload_post(d, post, row_offsets, n_reads, &hp);
   if (st != LVA_OK) return st;
   return bc_run(d, hp.dev, row_offsets, n_reads, &pat, 2, min_len, nullptr, nullptr, nullptr, out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// transition posteriors from a network's transition scores.
+// ---------------------------------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+// the limits of the basecall entry points, from the offsets alone: nothing is allocated for a batch that breaks them
+int tp_check(const int64_t* row_offsets, int32_t n, size_t* total) {
+  *total = 0;
+  if (n == 0) return LVA_OK;
+  if (row_offsets[0] != 0) return LVA_ERR_ARG;
+  for (int32_t i = 0; i < n; ++i)
+    if (row_offsets[i + 1] < row_offsets[i] || row_offsets[i + 1] - row_offsets[i] > kBcMaxBlocks) return LVA_ERR_ARG;
+  if (row_offsets[n] >= ((int64_t)1 << 31)) return LVA_ERR_ARG;
+  *total = (size_t)row_offsets[n];
+  return LVA_OK;
+}
+
+// forward and backward kernel over n reads resident on the device; post_dev may be scores_dev.  Enqueues only.
+int tp_run(lva_decoder* d, const float* scores_dev, const int64_t* row_offsets, int32_t n, size_t T, float* post_dev) {
+  if (((uintptr_t)scores_dev | (uintptr_t)post_dev) & 15u) return LVA_ERR_ARG;     // 16-byte row requests
+  if (T > d->tp_fwd_cap) {
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    if (d->d_tp_fwd) (void)hipFree(d->d_tp_fwd);
+    d->d_tp_fwd = nullptr; d->tp_fwd_cap = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&d->d_tp_fwd), T * 8 * sizeof(float)) != hipSuccess) return LVA_ERR_NOMEM;
+    d->tp_fwd_cap = T;
+  }
+  if ((size_t)n + 1 > d->tp_off_cap) {
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    if (d->d_tp_off) (void)hipFree(d->d_tp_off);
+    d->d_tp_off = nullptr; d->tp_off_cap = 0;
+    const size_t cap = std::max<size_t>((size_t)n + 1, 1024);
+    if (hipMalloc(reinterpret_cast<void**>(&d->d_tp_off), cap * sizeof(int64_t)) != hipSuccess) return LVA_ERR_NOMEM;
+    d->tp_off_cap = cap;
+  }
+  HIP_TRY(hipMemcpyAsync(d->d_tp_off, row_offsets, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipEventRecord(d->ev_total0, d->stream));
+  int e = launch_tp_forward(scores_dev, d->d_tp_off, n, d->d_tp_fwd, d->stream);
+  if (!e) e = launch_tp_backward(scores_dev, d->d_tp_off, n, d->d_tp_fwd, post_dev, d->stream);
+  if (e) { g_hip_error = hipGetErrorString((hipError_t)e); return LVA_ERR_HIP; }
+  HIP_TRY(hipEventRecord(d->ev_total1, d->stream));
+  return LVA_OK;
+}
+
+// the profile after a posterior call: the two kernels' HIP-event time and the blocks they covered
+int tp_profile(lva_decoder* d, size_t T, bool timed) {
+  const int32_t slots = d->prof.slots, kernel = d->prof.kernel;
+  d->prof = lva_profile{};
+  d->prof.slots = slots; d->prof.kernel = kernel;
+  d->prof.read_steps = T;
+  float ms = 0;
+  if (timed) HIP_TRY(hipEventElapsedTime(&ms, d->ev_total0, d->ev_total1));
+  d->prof.total_ms = ms;
+  return LVA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lva_transpost_batch_device(lva_decoder* d, const float* scores_dev, const int64_t* row_offsets, int32_t n_reads,
+                               float* post_dev) {
+  if (!d || n_reads < 0 || !row_offsets) return LVA_ERR_ARG;
+  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the decoder's HIP stream and the profile
+  size_t T = 0;
+  const int st = tp_check(row_offsets, n_reads, &T);
+  if (st != LVA_OK) return st;
+  if (T > 0 && (!scores_dev || !post_dev)) return LVA_ERR_ARG;
+  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
+  if (T == 0) return tp_profile(d, 0, false);
+  StreamDrain drain(d->stream);              // the offsets are copied from the caller's memory
+  const int rs = tp_run(d, scores_dev, row_offsets, n_reads, T, post_dev);
+  if (rs != LVA_OK) return rs;
+  drain.armed = false;
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  return tp_profile(d, T, true);
+}
+
+int lva_transpost_batch(lva_decoder* d, const float* scores, const int64_t* row_offsets, int32_t n_reads, float* post_out) {
+  if (!d || n_reads < 0 || !row_offsets) return LVA_ERR_ARG;
+  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the decoder's HIP stream and the profile
+  size_t T = 0;
+  int st = tp_check(row_offsets, n_reads, &T);
+  if (st != LVA_OK) return st;
+  if (T > 0 && (!scores || !post_out)) return LVA_ERR_ARG;
+  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
+  if (T == 0) return tp_profile(d, 0, false);
+  HostPost hp;
+  StreamDrain drain(d->stream);
+  st = upload_post(d, scores, row_offsets, n_reads, &hp);
+  if (st != LVA_OK) return st;
+  st = tp_run(d, hp.dev, row_offsets, n_reads, T, hp.dev);
+  if (st != LVA_OK) return st;
+  HIP_TRY(hipMemcpyAsync(post_out, hp.dev, T * 160, hipMemcpyDeviceToHost, d->stream));
+  drain.armed = false;
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  return tp_profile(d, T, true);
 }
 
 int lva_find_barcode_batch(lva_decoder* d, const char* bases, const uint32_t* trans, const int64_t* base_offsets,

@@ -81,6 +81,13 @@ class FakeDecoder:
     def stream(self, queue_cap=None):
         return _FakeStream(self, queue_cap or self.slots)
 
+    def posteriors(self, scores):
+        out = []
+        for s in scores:
+            s = np.ascontiguousarray(s, dtype=np.float32).reshape(-1, 40)
+            out.append((s - np.logaddexp.reduce(s.astype(np.float64), axis=1, keepdims=True)).astype(np.float32))
+        return out
+
     def profile(self):
         return dict(step_launches=self.launches, slots=self.slots)
 
@@ -186,6 +193,34 @@ class Server:
         self.config = _config(a)
         self.say("configuration %r resident: %d slots" % (self.config, self.dec.profile()["slots"]))
 
+    def posterior(self, conn, a, text, scores):
+        """-m posterior: scores -> .post on whatever decoder is resident (the code plays no part); its stream is empty and is
+        closed for the call, as lva_transpost_batch asks"""
+        try:
+            if self.dec is None:
+                mc, rate, msg_len = viterbi_nanopore.POSTERIOR_CODE
+                self.dec = self.decoder_cls(mc, rate, msg_len, device=self.device, max_slots=1)
+                self.config = (mc, rate, msg_len, 1, None, "", 0)
+                self.say("configuration %r resident for -m posterior" % (self.config,))
+            elif self.stream is not None:
+                self.stream.close()
+            self.stream = None
+            post = self.dec.posteriors([scores])[0]
+            self.stream = self.dec.stream()
+            viterbi_nanopore.write_post(a.outfile, post)
+        except (LvaError, OSError) as e:
+            if self.dec is not None and self.stream is None:
+                try:
+                    self.stream = self.dec.stream()
+                except LvaError:
+                    self.close_decoder()
+            self.answer(conn, 1, text, "viterbi_nanopore: %s\n" % e)
+            return
+        self.reads += 1
+        self.blocks += int(scores.shape[0])
+        self.last_work = time.monotonic()
+        self.answer(conn, 0, text)
+
     def feed(self):
         """backlog -> stream, in arrival order; a request for another configuration waits (and holds back those behind it)
         until the stream is empty"""
@@ -198,6 +233,12 @@ class Server:
                     self.backlog.popleft()
                     self.answer(conn, 134, text)
                     continue
+            if a.mode == "posterior":        # (extension) answered by the resident decoder, between streams
+                if self.jobs:
+                    return                   # the batch entry points are busy while reads are in the stream
+                self.backlog.popleft()
+                self.posterior(conn, a, text, post)
+                continue
             if self.config != _config(a):
                 if self.jobs:
                     return

@@ -134,6 +134,7 @@ class Decoder:
             raise LvaError(st, self._L.lva_last_hip_error().decode())
         self._h = h
         self.mem_conv, self.rate, self.msg_len, self.list_size = mem_conv, rate, msg_len, list_size
+        self.device = device
 
     def close(self):
         if getattr(self, "_h", None):
@@ -314,6 +315,89 @@ class Decoder:
         for i, r in zip(good, dec):
             out[i] = (loc[i], r)
         return out
+
+    # --- transition posteriors from a network's transition scores ---------------
+    def posteriors(self, scores):
+        """scores: list of float32 [nblk_i, 40] transition-score matrices of a flip-flop CRF (flappie's `trans` layout,
+        which is the .post layout) -> list of float32 [nblk_i, 40] log-posteriors, what flappie writes to a .post file
+        (transpost_crf_flipflop, flappie/src/decode.c:377-497)"""
+        flat, off = self._pack(scores)
+        out = np.empty_like(flat)
+        self._check(self._L.lva_transpost_batch(self._h, flat.ctypes.data, off.ctypes.data, len(off) - 1, out.ctypes.data))
+        return [out[off[i]:off[i + 1]].copy() for i in range(len(off) - 1)]
+
+    def posteriors_resident(self, dev_ptr, off, out_ptr=None):
+        """posteriors of a resident score buffer (upload()); out_ptr=None: in place, the scores are overwritten"""
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        self._check(self._L.lva_transpost_batch_device(self._h, dev_ptr, off.ctypes.data, len(off) - 1,
+                                                       dev_ptr if out_ptr is None else out_ptr))
+
+    def alloc(self, nbytes):
+        p = ctypes.c_void_p()
+        self._check(self._L.lva_device_alloc(self._h, int(nbytes), ctypes.byref(p)))
+        return p
+
+    def download(self, dev_ptr, off):
+        """a resident [off[-1], 40] float32 buffer -> list of host matrices"""
+        flat = np.empty((int(off[-1]), 40), np.float32)
+        self._check(self._L.lva_device_download(self._h, flat.ctypes.data, dev_ptr, flat.nbytes))
+        return [flat[off[i]:off[i + 1]].copy() for i in range(len(off) - 1)]
+
+    def _decode_chain_resident(self, dev, off, rc, start_barcode, end_barcode):
+        n = len(off) - 1
+        if start_barcode is None and end_barcode is None:
+            return self.decode_resident(dev, off, rc)
+        if start_barcode is None or end_barcode is None or rc is not None:
+            raise ValueError("give both barcodes (the orientation is then found, not passed), or neither")
+        loc = self.locate_payload_resident(dev, off, start_barcode, end_barcode)
+        good = [i for i in range(n) if loc[i]["ok"]]
+        dec = self.decode_windows_resident(dev, [off[i] + loc[i]["start_pos"] for i in good],
+                                           [loc[i]["end_pos"] - loc[i]["start_pos"] + 1 for i in good],
+                                           rc=[loc[i]["rc"] for i in good]) if good else []
+        out = [(loc[i], None) for i in range(n)]
+        for i, r in zip(good, dec):
+            out[i] = (loc[i], r)
+        return out
+
+    def decode_from_scores(self, scores, rc=None, start_barcode=None, end_barcode=None, offsets=None):
+        """scores -> posteriors -> (barcode localisation ->) decoded lists without leaving the device: the scores are
+        uploaded once, turned into posteriors in place and decoded where they are.  Returns what decode() returns, or with
+        both barcodes what decode_with_barcodes() returns.
+        scores: a list of float32 [nblk_i, 40] matrices, or ONE contiguous float32 torch tensor [total_blocks, 40] on the
+        decoder's device with `offsets` (int64 [n + 1] block offsets): its memory is read where it is and not modified --
+        the posteriors go to a buffer of the decoder's.  (A process that uses torch and this library initialises torch's
+        device first: INTEGRATION.md section 2.)"""
+        if isinstance(scores, (list, tuple)) or isinstance(scores, np.ndarray):
+            if offsets is not None:
+                flat, off = np.ascontiguousarray(scores, dtype=np.float32).reshape(-1, 40), np.ascontiguousarray(offsets, dtype=np.int64)
+                dev = self.alloc(flat.nbytes)
+                self._check(self._L.lva_device_upload(self._h, dev, flat.ctypes.data, flat.nbytes))
+            else:
+                dev, off = self.upload(scores)
+            try:
+                self.posteriors_resident(dev, off)
+                return self._decode_chain_resident(dev, off, rc, start_barcode, end_barcode)
+            finally:
+                self.free(dev)
+        import torch                              # only here: the package imports without torch
+        if not isinstance(scores, torch.Tensor):
+            raise TypeError("scores: a list of [nblk, 40] arrays or one torch tensor with offsets")
+        if offsets is None:
+            raise ValueError("a score tensor needs offsets")
+        if scores.dtype != torch.float32 or not scores.is_contiguous() or scores.dim() != 2 or scores.shape[1] != 40:
+            raise ValueError("score tensor: float32, contiguous, [total_blocks, 40]")
+        if not scores.is_cuda or scores.device.index != self.device:
+            raise ValueError("score tensor is on %s, the decoder on device %d" % (scores.device, self.device))
+        off = np.ascontiguousarray(offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets, dtype=np.int64)
+        if int(off[-1]) != scores.shape[0]:
+            raise ValueError("offsets end at %d, the tensor has %d blocks" % (int(off[-1]), scores.shape[0]))
+        torch.cuda.current_stream(scores.device).synchronize()     # the decoder works on a stream of its own
+        dev = self.alloc(scores.shape[0] * 160)
+        try:
+            self.posteriors_resident(ctypes.c_void_p(scores.data_ptr()), off, out_ptr=dev)
+            return self._decode_chain_resident(dev, off, rc, start_barcode, end_barcode)
+        finally:
+            self.free(dev)
 
     # --- decode stream: reads go in one at a time, results come out as they finish -------------
     def stream(self, queue_cap=None):

@@ -30,6 +30,7 @@ Beyond the reference:
              gathers the lists (sharding.decode_sharded) and writes every output file.
 """
 import argparse
+import ctypes
 import os
 import sys
 
@@ -57,6 +58,10 @@ def build_parser():
     p.add_argument("--end_barcode", type=str, default=None)
     p.add_argument("--max_deviation", type=int, default=20)
     p.add_argument("--device", type=int, default=0)
+    p.add_argument("--input_kind", choices=["post", "scores"], default="post",
+                   help="what the manifest's files hold: .post transition posteriors (flappie --post-output-file), or the raw "
+                        "transition scores of a flip-flop CRF network in the same float32 [nblk][40] layout -- turned into "
+                        "posteriors on the device (transpost_crf_flipflop, flappie/src/decode.c:377-497) before anything else")
     p.add_argument("--resume", action="store_true")
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--chunk", type=int, default=4096, help="reads decoded (and written) per pass over the manifest")
@@ -89,6 +94,8 @@ def decode_rows(args, rows, dec):
     located = {}
     if not rows:
         return results, located
+    if getattr(args, "input_kind", "post") == "scores":
+        return decode_score_rows(args, rows, dec, min_len)
     # rows without a window: basecall + barcode search + decode on the device (:68-89)
     todo = [i for i, r in enumerate(rows) if r[3] is None]
     if todo:
@@ -105,6 +112,45 @@ def decode_rows(args, rows, dec):
         posts = (helper.truncate_post(helper.read_post_file(rows[i][2]), rows[i][3], rows[i][4]) for i in keep)
         for j, res in dec.decode_iter(posts, rc=(rows[i][5] for i in keep)):
             results[keep[j]] = res
+    return results, located
+
+
+def decode_score_rows(args, rows, dec, min_len):
+    """decode_rows for files of raw transition scores: the chunk is uploaded once and turned into posteriors in place (the
+    posteriors of a block depend on the whole read, so windows are cut afterwards); from there on the rows are handled as
+    untruncated .post files are -- barcode search + windows for rows without a block range, the given windows otherwise"""
+    results = [BARCODE_FAILURE] * len(rows)
+    located = {}
+    dev, off = dec.upload([helper.read_post_file(r[2]) for r in rows])
+    try:
+        dec.posteriors_resident(dev, off)
+        todo = [i for i, r in enumerate(rows) if r[3] is None]
+        win = {}                                               # row -> (first block in the buffer, blocks, rc)
+        if todo:
+            if len(todo) == len(rows):
+                loc = dec.locate_payload_resident(dev, off, args.start_barcode, args.end_barcode)
+            else:                                              # mixed manifest: the rows to search, one read per call
+                loc = []
+                for i in todo:
+                    one = np.array([0, off[i + 1] - off[i]], np.int64)
+                    loc += dec.locate_payload_resident(ctypes.c_void_p(dev.value + int(off[i]) * 160), one,
+                                                       args.start_barcode, args.end_barcode)
+            for i, lc in zip(todo, loc):
+                located[i] = dict(start_pos=int(lc["start_pos"]), end_pos=int(lc["end_pos"]), rc=bool(lc["rc"]))
+                if lc["ok"]:
+                    win[i] = (int(off[i]) + lc["start_pos"], lc["end_pos"] - lc["start_pos"] + 1, lc["rc"])
+        for i, r in enumerate(rows):
+            if r[3] is not None and not (r[3] == -1 or r[4] - r[3] + 1 < min_len):
+                assert r[3] >= 0 and off[i + 1] - off[i] >= r[4] + 1     # helper.truncate_post
+                win[i] = (int(off[i]) + r[3], r[4] - r[3] + 1, r[5])
+        order = sorted(win)
+        if order:
+            dec_res = dec.decode_windows_resident(dev, [win[i][0] for i in order], [win[i][1] for i in order],
+                                                  rc=[win[i][2] for i in order])
+            for i, res in zip(order, dec_res):
+                results[i] = res
+    finally:
+        dec.free(dev)
     return results, located
 
 

@@ -204,7 +204,7 @@ def encode(data_file, oligo_file, bytes_per_oligo, RS_redundancy, conv_m, conv_r
 
 def simulate_and_decode(oligo_file, decoded_data_file, num_reads, data_file_size, bytes_per_oligo, RS_redundancy, conv_m, conv_r,
                         pad=False, syn_sub_prob=0.005, syn_del_prob=0.005, syn_ins_prob=0.0005, deepsimdwell=False, num_thr=16,
-                        list_size=1, seed=None, margin=6.0, device=0, out=None, decoder=None):
+                        list_size=1, seed=None, margin=6.0, device=0, out=None, decoder=None, posterior_source="softmax"):
     """helper.py:275-350, same arguments: num_reads times pick a random oligo and orientation, pass it through the
     substitution / deletion / insertion channel, turn it into a posterior matrix, decode a list of list_size candidates,
     take the first candidate whose CRC-8 checks and whose index is in range (the first payload seen for an index stands,
@@ -212,6 +212,9 @@ def simulate_and_decode(oligo_file, decoded_data_file, num_reads, data_file_size
     The signal simulator and the basecaller network of the reference (scrappy, flappie) are replaced by
     synth.posteriors_from_bases (`margin`: how far the true transition stands out); all reads are decoded in ONE batch
     on the GPU instead of one decoder process per read.  seed: numpy seed (the reference draws from the global state).
+    posterior_source: "softmax" -- every block's posteriors are the log-softmax of independent logits; "crf" -- what a
+    flip-flop CRF network gives: transition scores (synth.scores_from_bases) that go through Decoder.decode_from_scores,
+    forward-backward posteriors and decode without leaving the device.
     -> dict(num_attempted, num_success, num_unique, decoded bytes)."""
     import sys
     from . import rs_code, synth
@@ -222,6 +225,9 @@ def simulate_and_decode(oligo_file, decoded_data_file, num_reads, data_file_size
     with open(oligo_file) as f:
         oligo_list = [ln.rstrip("\n") for ln in f.readlines()]
     print("oligo_len", len(oligo_list[0]), file=out)
+    if posterior_source not in ("softmax", "crf"):
+        raise ValueError("posterior_source: 'softmax' or 'crf'")
+    crf = posterior_source == "crf"
     rng = np.random.default_rng(seed)
     posts, rcs = [], []
     for _ in range(num_reads):
@@ -230,12 +236,12 @@ def simulate_and_decode(oligo_file, decoded_data_file, num_reads, data_file_size
         if rc:
             oligo = reverse_complement(oligo)
         seq = synth.mutate(synth.bases_from_str(oligo), rng, syn_sub_prob, syn_del_prob, syn_ins_prob)
-        posts.append(synth.posteriors_from_bases(seq, rng, margin=margin))
+        posts.append(synth.scores_from_bases(seq, rng, margin=margin) if crf else synth.posteriors_from_bases(seq, rng, margin=margin))
         rcs.append(rc)
     own = decoder is None
     dec = Decoder(conv_m, conv_r, msg_len, list_size=list_size, max_deviation=20, device=device) if own else decoder
     try:
-        results = dec.decode(posts, rc=rcs)
+        results = dec.decode_from_scores(posts, rc=rcs) if crf else dec.decode(posts, rc=rcs)
     finally:
         if own:
             dec.close()

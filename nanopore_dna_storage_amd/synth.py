@@ -68,8 +68,9 @@ def transition_index(frm, to):
     return to * 8 + frm if to < FLOP else 32 + frm
 
 
-def posteriors_from_bases(bases, rng, margin=6.0, sigma=1.5, mean_extra_dwell=3.4, quantum=None):
-    """bases (0..3) -> float32 [nblk, 40] log-posteriors."""
+def true_transitions(bases, rng, mean_extra_dwell=3.4):
+    """index (0..39) of the true transition of every block: one leading stay block, then per base the transition into
+    its state and 1 + Poisson(mean_extra_dwell) - 1 stays"""
     states = state_path(bases)
     first = int(states[0])
     lead = (first % 4 + 1 + int(rng.integers(0, 3))) % 4       # a flip state of another base
@@ -81,6 +82,12 @@ def posteriors_from_bases(bases, rng, margin=6.0, sigma=1.5, mean_extra_dwell=3.
         for _ in range(int(rng.poisson(mean_extra_dwell))):
             true_idx.append(transition_index(st, st))
         cur = st
+    return np.asarray(true_idx)
+
+
+def posteriors_from_bases(bases, rng, margin=6.0, sigma=1.5, mean_extra_dwell=3.4, quantum=None):
+    """bases (0..3) -> float32 [nblk, 40] log-posteriors."""
+    true_idx = true_transitions(bases, rng, mean_extra_dwell)
     nblk = len(true_idx)
     logits = rng.normal(0.0, sigma, size=(nblk, 40))
     logits[np.arange(nblk), np.asarray(true_idx)] += margin
@@ -90,6 +97,22 @@ def posteriors_from_bases(bases, rng, margin=6.0, sigma=1.5, mean_extra_dwell=3.
     mx = logits.max(axis=1, keepdims=True)
     lse = mx + np.log(np.exp(logits - mx).sum(axis=1, keepdims=True))
     return (logits - lse).astype(np.float32)
+
+
+SCORE_CLIP = 5.0    # flappie's output layer is 5 tanh(.) at temperature 1 (flappie/src/layers.c:1081-1082)
+
+
+def scores_from_bases(bases, rng, margin=6.0, sigma=1.5, mean_extra_dwell=3.4, return_path=False):
+    """bases (0..3) -> float32 [nblk, 40] transition SCORES as a flip-flop CRF network emits them (flappie's `trans`
+    matrix, the input of transpost_crf_flipflop): noise N(0, sigma^2) on all 40 entries of a block, +margin on the true
+    path's transition, clipped to the range of the network's output layer.  Nothing is normalised -- the posteriors of
+    a block depend on the whole read (Decoder.posteriors).  return_path: -> (scores, true transition index per block)."""
+    true_idx = true_transitions(bases, rng, mean_extra_dwell)
+    nblk = len(true_idx)
+    scores = rng.normal(0.0, sigma, size=(nblk, 40))
+    scores[np.arange(nblk), true_idx] += margin
+    scores = np.clip(scores, -SCORE_CLIP, SCORE_CLIP).astype(np.float32)
+    return (scores, true_idx) if return_path else scores
 
 
 def make_read(mem_conv, rate, msg_len, seed, rc=False, margin=6.0, sub=0.0, dele=0.0, ins=0.0, quantum=None):
@@ -102,6 +125,18 @@ def make_read(mem_conv, rate, msg_len, seed, rc=False, margin=6.0, sub=0.0, dele
         seq = mutate(seq, rng, sub, dele, ins)
     post = posteriors_from_bases(seq, rng, margin=margin, quantum=quantum)
     return dict(msg=msg, oligo=oligo, read_bases=seq, post=post, rc=bool(rc), seed=seed)
+
+
+def make_read_scores(mem_conv, rate, msg_len, seed, rc=False, margin=6.0, sub=0.0, dele=0.0, ins=0.0):
+    """make_read with transition scores in place of posteriors -> dict(msg, oligo, read_bases, scores, true_idx, rc)"""
+    rng = np.random.default_rng(seed)
+    msg = rng.integers(0, 2, size=msg_len, dtype=np.uint8)
+    oligo = encode(mem_conv, rate, msg_len, msg)
+    seq = reverse_complement_bases(oligo) if rc else oligo
+    if sub or dele or ins:
+        seq = mutate(seq, rng, sub, dele, ins)
+    scores, true_idx = scores_from_bases(seq, rng, margin=margin, return_path=True)
+    return dict(msg=msg, oligo=oligo, read_bases=seq, scores=scores, true_idx=true_idx, rc=bool(rc), seed=seed)
 
 
 BASES = "ACGT"
@@ -128,6 +163,23 @@ def make_barcoded_read(mem_conv, rate, msg_len, seed, start_barcode, end_barcode
         strand = mutate(strand, rng, sub, dele, ins)
     post = posteriors_from_bases(strand, rng, margin=margin)
     return dict(msg=msg, oligo=oligo, strand=strand, post=post, rc=bool(rc), seed=seed)
+
+
+def make_barcoded_read_scores(mem_conv, rate, msg_len, seed, start_barcode, end_barcode, rc=False, margin=6.0,
+                              flank=(10, 40), sub=0.0, dele=0.0, ins=0.0):
+    """make_barcoded_read with transition scores in place of posteriors -> dict(msg, oligo, strand, scores, true_idx, rc)"""
+    rng = np.random.default_rng(seed)
+    msg = rng.integers(0, 2, size=msg_len, dtype=np.uint8)
+    oligo = encode(mem_conv, rate, msg_len, msg)
+    f5 = rng.integers(0, 4, size=int(rng.integers(flank[0], flank[1] + 1)), dtype=np.uint8)
+    f3 = rng.integers(0, 4, size=int(rng.integers(flank[0], flank[1] + 1)), dtype=np.uint8)
+    strand = np.concatenate([f5, bases_from_str(start_barcode), oligo, bases_from_str(end_barcode), f3]).astype(np.uint8)
+    if rc:
+        strand = reverse_complement_bases(strand)
+    if sub or dele or ins:
+        strand = mutate(strand, rng, sub, dele, ins)
+    scores, true_idx = scores_from_bases(strand, rng, margin=margin, return_path=True)
+    return dict(msg=msg, oligo=oligo, strand=strand, scores=scores, true_idx=true_idx, rc=bool(rc), seed=seed)
 
 
 def make_reads(mem_conv, rate, msg_len, n, seed0=0, rc_mode="none", margin=6.0, **kw):

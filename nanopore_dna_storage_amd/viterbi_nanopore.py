@@ -57,6 +57,13 @@ Usage:
   -t, --num-thr arg        Number of threads for convolutional code decoding
                            (default 1) (default: 1)
   -h, --help               Display this message
+
+ Extension (not in the reference executable):
+  -m posterior             Infile: float32 [nblk][40] transition scores of a
+                           flip-flop CRF network; outfile: the .post file of
+                           their log-posteriors (flappie's
+                           transpost_crf_flipflop), which -m decode reads.
+                           Needs no code parameters.
 """
 
 _PARAM_MESSAGES = {
@@ -101,9 +108,13 @@ def front(argv, out, cwd=None):
     if not a.mode or not a.infile or not a.outfile:
         print("Invalid options.", file=out); print(USAGE, file=out)
         return 255, None
-    if a.mode not in ("encode", "decode"):
+    if a.mode not in ("encode", "decode", "posterior"):
         print("Invalid mode.", file=out); print(USAGE, file=out)
         return 255, None
+    if a.mode == "posterior":                     # extension: nothing of the code is involved
+        if cwd is not None:
+            a.infile, a.outfile = os.path.join(cwd, a.infile), os.path.join(cwd, a.outfile)
+        return None, (a, False)
     if a.mem_conv is None:
         print("Memory of convolutional code not specified.", file=out); print(USAGE, file=out)
         return 255, None
@@ -141,6 +152,14 @@ def front(argv, out, cwd=None):
     return None, (a, rc)
 
 
+POSTERIOR_CODE = (6, 1, 8)       # -m posterior needs a decoder handle, not a code: the smallest one (mem_conv, rate, msg_len)
+
+
+def write_post(path, post):
+    """a .post file as flappie writes it (flappie.c:266-271): the float32 matrix, block after block"""
+    np.ascontiguousarray(post, dtype="<f4").tofile(path)
+
+
 def write_list(path, msgs):
     with open(path, "w") as f:                    # :248-253
         for row in msgs:
@@ -160,6 +179,14 @@ def main(argv=None, out=sys.stdout):
         post = helper.read_post_file(a.infile)
     except OSError:
         return 134
+    if a.mode == "posterior":
+        try:
+            with Decoder(*POSTERIOR_CODE, device=a.device, max_slots=1) as dec:
+                write_post(a.outfile, dec.posteriors([post])[0])
+        except (LvaError, OSError) as e:
+            print("viterbi_nanopore: %s" % e, file=sys.stderr)
+            return 1
+        return 0
     try:
         with Decoder(a.mem_conv, a.rate, a.msg_len, list_size=a.list_size, max_deviation=a.max_deviation,
                      sync_marker=a.sync_marker, sync_period=a.sync_period, device=a.device, max_slots=1) as dec:
