@@ -1,5 +1,7 @@
 """SURVEY 8(f) row N3 on the GPU: bc_basecall / bc_search / bc_finalize through the C ABI against the
-CPU oracle (integer and fp32 add/compare work: results must be identical)."""
+CPU oracle (integer and fp32 add/compare work: results must be identical).  The second half of the file takes bc_search
+past one pass of its 256 threads (sequences of 600 .. 6000 bases, equal and near-equal minima seen by the same thread in
+different passes and by neighbouring wavefronts) and bc_basecall to 200 000 and 2^20 blocks, the limit of the API."""
 import numpy as np
 import pytest
 
@@ -135,6 +137,121 @@ def test_post_to_list_chain_on_device(oracle, dec):
         assert np.array_equal(res[0], wm) and np.array_equal(res[1].view(np.uint32), ws.view(np.uint32))
         assert np.array_equal(res[0][0], x["msg"])          # and the chain recovers the message
     assert n_ok >= 5
+
+
+# ---------------------------------------------------------------- beyond one pass of 256 windows per workgroup
+LONG = (600, 1025, 2049, 6000)            # each half holds > 256, > 512, > 1024 and > 2048 windows
+_WANT = {}                                # case id -> oracle.find_barcode_pos (pure-Python edit distances: the cost of these tests)
+
+
+def _plant(s, at, word):
+    return s[:at] + word + s[at + len(word):]
+
+
+def _one_edit(word):
+    k = len(word) // 2
+    return word[:k] + "ACGT"[("ACGT".index(word[k]) + 1) % 4] + word[k + 1:]
+
+
+def _long_cases():
+    """-> [(id, sequence, trans, which barcode is planted | None)].  Window i of a half is searched by thread i % 256 in pass
+    i // 256: copies planted 256 windows apart meet in one thread, copies 64 apart in neighbouring wavefronts.  `same`: two
+    exact copies, the FIRST must win; `later`: the first copy carries one substitution, the later, exact one must win."""
+    cases = []
+    for n in LONG:
+        rng = np.random.default_rng([13, n])
+        trans = np.cumsum(rng.integers(1, 9, n)) + 1
+        rnd = "".join("ACGT"[i] for i in rng.integers(0, 4, n))
+        cases.append(("random-%d" % n, rnd, trans, None))
+        cases.append(("allA-%d" % n, "A" * n, trans, None))
+        for which, word, base, nwin in (("start", SB, 0, n // 2 + 1 - len(SB)), ("end", EB, n // 2, n - len(EB) - n // 2)):
+            for gap in (256, 64):
+                i = int(rng.integers(0, nwin - gap))
+                for kind in ("same", "later"):
+                    first = word if kind == "same" else _one_edit(word)
+                    s = _plant(_plant(rnd, base + i, first), base + i + gap, word)
+                    assert len(s) == n
+                    cases.append(("%s-%s-gap%d-%d" % (which, kind, gap, n), s, trans, which))
+    return cases
+
+
+def _want_barcode(oracle, case):
+    cid, s, trans, which = case
+    if cid not in _WANT:
+        _WANT[cid] = oracle.find_barcode_pos(s, trans, SB, EB)
+        if which:                                                # the exact copy is found
+            assert _WANT[cid][2 if which == "start" else 3] == 0 and _WANT[cid][0] >= 0, cid
+    return _WANT[cid]
+
+
+def _tuple(g):
+    return (g["start_pos"], g["end_pos"], g["dist_start"], g["dist_end"])
+
+
+@pytest.mark.parametrize("n", LONG)
+def test_find_barcode_long_sequences_one_by_one(oracle, dec, n):
+    cases = [c for c in _long_cases() if c[0].endswith("-%d" % n)]
+    assert len(cases) == 10
+    for c in cases:
+        assert _tuple(dec.find_barcode([c[1]], [c[2]], SB, EB)[0]) == _want_barcode(oracle, c), c[0]
+    # "A" * n: every window of a half has the same distance, window 0 of each half wins
+    a = _want_barcode(oracle, cases[1])
+    assert a[0] == int(cases[1][2][len(SB)]) - 1 and a[1] == int(cases[1][2][n // 2 - 1]) - 1
+
+
+def test_find_barcode_long_sequences_in_one_batch(oracle, dec):
+    cases = _long_cases()
+    got = dec.find_barcode([c[1] for c in cases], [c[2] for c in cases], SB, EB)
+    assert len(got) == len(cases) == 40
+    for c, g in zip(cases, got):
+        assert _tuple(g) == _want_barcode(oracle, c), c[0]
+
+
+@pytest.mark.parametrize("rc", [False, True])
+def test_locate_payload_long_flanks(oracle, dec, rc):
+    """flanks of 450 .. 480 bases in front of the barcodes: the winning window lies beyond the first pass of its half.
+    (The 35-base oligo and its barcodes straddle the middle of the read only while the flanks differ by at most 35.)"""
+    reads = [synth.make_barcoded_read(8, 3, 44, 900 + i, SB, EB, rc=rc, margin=6.0, flank=(450, 480)) for i in range(3)]
+    got = dec.locate_payload([x["post"] for x in reads], SB, EB)
+    for x, g in zip(reads, got):
+        want = oracle.locate_payload(x["post"], SB, EB, 8 + 44 + 1)
+        assert g == {k: want[k] for k in ("ok", "start_pos", "end_pos", "rc", "dist_start", "dist_end")}
+        assert want["ok"] and want["rc"] == rc
+        s_first = int(np.searchsorted(want["trans"], want["start_pos"] + 1)) - len(SB)      # trans[s_last + 1] - 1 == start_pos
+        assert s_first >= 256 and len(want["basecall"]) >= 900
+
+
+def test_basecall_long_matrices_in_a_batch_with_short_ones(oracle, dec):
+    """200 000 random blocks and 2^20 blocks (the limit) on a grid of half-integers, where many comparisons are draws, in one
+    batch with reads of 1, 7 and 9 blocks -- the long reads share a wavefront with reads that end at once -- and of 2 .. 16
+    blocks, so that the traceback's chunks of 8 rows end on every remainder."""
+    rng = np.random.default_rng(14)
+    long_random = rng.normal(0, 2, (200000, 40)).astype(np.float32)
+    grid = (np.round(rng.normal(0, 2, (1 << 20, 40)) * 2) / 2).astype(np.float32)
+    short = {n: rng.normal(0, 2, (n, 40)).astype(np.float32) for n in range(1, 17)}
+    posts = [short[1], long_random, short[7], grid, short[9]] + [short[n] for n in range(2, 17)]
+    got = dec.basecall(posts)
+    assert len(got) == len(posts)
+    for p, (bc, trans) in zip(posts, got):
+        want_bc, want_trans, _, _ = oracle.basecall(p)
+        assert bc == want_bc
+        assert np.array_equal(trans, want_trans)
+        assert len(p) < 200000 or len(want_bc) > len(p) // 8       # the long reads call many bases
+
+
+def test_block_limit(dec):
+    """2^20 blocks or bases per read are served (above); one more is LVA_ERR_ARG, decided from the offsets before any launch"""
+    limit = 1 << 20
+    dev, _ = dec.upload([np.zeros((10, 40), np.float32)])
+    try:
+        with pytest.raises(pkg.LvaError) as e:
+            dec.basecall_resident(dev, np.array([0, limit + 1], np.int64))
+        assert e.value.code == -10
+    finally:
+        dec.free(dev)
+    with pytest.raises(pkg.LvaError) as e:
+        dec.find_barcode(["A" * (limit + 1)], [np.arange(1, limit + 2)], SB, EB)
+    assert e.value.code == -10
 
 
 def test_argument_errors_and_empty_batches(dec):
