@@ -324,6 +324,61 @@ int lva_rs_encode(int32_t device, const uint16_t *data, int32_t n_codewords, int
                   uint16_t pad_symbol, uint16_t *out);
 const char *lva_rs_last_error(void);
 
+/* ---------------------------------------------------------------------------------------------
+ * what happens to a decoded list -- the step between lva_decode_batch and
+ * lva_rs_decode.  Inputs are the decoder's own outputs, as they are:
+ *   msgs    uint8 [n_reads][list_size][msg_len] of 0/1, best first (only bit 0 of a byte is looked at);
+ *   counts  int32 [n_reads]; a count <= 0 (a negative LVA_ERR_* included) means "no list", a count above list_size
+ *           counts as list_size.
+ * 1 <= msg_len <= 255, list_size >= 1, n_reads * list_size * msg_len < 2^31; n_reads = 0 succeeds and touches nothing.
+ * Like lva_rs_decode the calls take a device ordinal, not a decoder: they work on a stream of their own, are complete
+ * on return and leave every lva_profile alone.  All results are integers and exact; the same inputs give the same
+ * bytes on every run.  Arguments are checked before the device is touched (LVA_ERR_ARG); without a gfx950 device
+ * the calls return LVA_ERR_NO_DEVICE (no CPU path); a HIP failure is LVA_ERR_HIP with the text in lva_last_hip_error.
+ * ------------------------------------------------------------------------------------------- */
+
+/* replaces: helper.decode_list_CRC_index (helper.py:371-388) for every read of a batch.
+ * Of read i the first min(counts[i], use_entries) entries are tried in order (use_entries = 0: list_size; the
+ * `[:list_size]` slices of compute_error_rate_from_decoded_lists.py:37 and decode_RS_from_decoded_lists.py:41).  An entry
+ * is accepted when -- without its last bit if pad -- the CRC-8 (polynomial 0x07, start 0, not reflected, no final xor)
+ * of all its bytes but the last equals the last byte, and its first 12 bits x give an index
+ * 3303 * (x - 2532) mod 4096 (helper.py:28-32) below num_oligos.  msg_len must be 12 + 8 * bytes_per_oligo + 8 + (pad ? 1 : 0),
+ * the one shape helper.compute_parameters (helper.py:352-363) produces; 1 <= num_oligos <= 4096.
+ *   out_index   [n_reads] index of the accepted entry, -1: none;
+ *   out_rank    [n_reads] its place in the list, -1: none;
+ *   out_payload [n_reads][bytes_per_oligo] its payload, zeros: none. */
+int lva_list_filter(int32_t device, const uint8_t *msgs, const int32_t *counts, int32_t n_reads, int32_t list_size,
+                    uint32_t msg_len, int32_t use_entries /* 0 = list_size */, int32_t bytes_per_oligo, int32_t num_oligos,
+                    int32_t pad, int32_t *out_index, int32_t *out_rank, uint8_t *out_payload);
+
+/* replaces: the per-index vote of decode_RS_from_decoded_lists.py:37-51 over lva_list_filter's outputs; with first_only
+ * the rule of helper.simulate_and_decode instead (helper.py:326-329: the first payload seen for an index stands).
+ *   index [n_reads], payload [n_reads][bytes_per_oligo] in read order; a negative index is a read without a vote,
+ *   an index >= num_oligos is LVA_ERR_ARG.  1 <= num_oligos <= 4096, n_reads * bytes_per_oligo < 2^31.
+ * Per index the payload with the most votes wins, among equal counts the one that reached that count first in read
+ * order (what the reference's stable re-sort after every read gives).
+ *   out_present [num_oligos] 1: some read voted for the index;
+ *   out_payload [num_oligos][bytes_per_oligo] the winner, zeros where absent;
+ *   out_votes   [num_oligos] reads that carried the winner, 0 where absent.
+ * The rows with out_present = 1 are lva_rs_decode's received reads, the others its erasures. */
+int lva_list_consensus(int32_t device, const int32_t *index, const uint8_t *payload, int32_t n_reads, int32_t bytes_per_oligo,
+                       int32_t num_oligos, int32_t first_only, uint8_t *out_present, uint8_t *out_payload, int32_t *out_votes);
+
+/* Per-read statistics of a decoded list against the message that was sent.
+ * replaces: the per-trial part of simulator.py:92-110 (distance.hamming, distance.levenshtein, the 8- and 16-bit block
+ * comparisons).  All fields are -1 for a read without a list. */
+typedef struct lva_list_stat {
+  int32_t top_correct;  /* the first entry equals the truth */
+  int32_t list_correct; /* one of the counts[i] entries does */
+  int32_t hamming;      /* differing bits of the first entry */
+  int32_t hamming8;     /* differing blocks of 8 bits (the last block may be short) */
+  int32_t hamming16;    /* differing blocks of 16 bits */
+  int32_t edit;         /* unit-cost Levenshtein distance between truth and first entry */
+} lva_list_stat;
+/* truth: uint8 [n_reads][msg_len] of 0/1; out [n_reads]. */
+int lva_list_stats(int32_t device, const uint8_t *msgs, const int32_t *counts, const uint8_t *truth, int32_t n_reads,
+                   int32_t list_size, uint32_t msg_len, lva_list_stat *out);
+
 #ifdef __cplusplus
 }
 #endif

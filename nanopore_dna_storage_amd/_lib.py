@@ -28,6 +28,7 @@ EXPORTS = [
     "lva_rs_decode", "lva_rs_encode", "lva_rs_last_error",
     "lva_stream_open", "lva_stream_close", "lva_stream_submit", "lva_stream_poll", "lva_stream_pending",
     "lva_transpost_batch", "lva_transpost_batch_device", "lva_device_download",
+    "lva_list_filter", "lva_list_consensus", "lva_list_stats",
 ]
 
 
@@ -74,6 +75,11 @@ class Profile(ctypes.Structure):
 class PayloadPos(ctypes.Structure):
     _fields_ = [("start_pos", ctypes.c_int32), ("end_pos", ctypes.c_int32), ("dist_start", ctypes.c_int32),
                 ("dist_end", ctypes.c_int32), ("rc", ctypes.c_int32), ("ok", ctypes.c_int32)]
+
+
+class ListStat(ctypes.Structure):
+    _fields_ = [("top_correct", ctypes.c_int32), ("list_correct", ctypes.c_int32), ("hamming", ctypes.c_int32),
+                ("hamming8", ctypes.c_int32), ("hamming16", ctypes.c_int32), ("edit", ctypes.c_int32)]
 
 
 _lib = None
@@ -151,5 +157,11 @@ def load_library():
     L.lva_transpost_batch.argtypes = [vp, vp, vp, i32, vp]
     L.lva_transpost_batch_device.argtypes = [vp, vp, vp, i32, vp]
     L.lva_device_download.argtypes = [vp, vp, vp, u64]
+    for name in ("lva_list_filter", "lva_list_consensus", "lva_list_stats"):
+        if not hasattr(L, name):                     # additive again: same ABI version
+            raise ImportError("%s has no list consumers (%s): rebuild it" % (path, name))
+    L.lva_list_filter.argtypes = [i32, vp, vp, i32, i32, u32, i32, i32, i32, i32, vp, vp, vp]
+    L.lva_list_consensus.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.lva_list_stats.argtypes = [i32, vp, vp, vp, i32, i32, u32, vp]
     _lib = L
     return L

@@ -17,6 +17,9 @@ def build_parser():
     p.add_argument("--conv_input_file", type=str, required=True)
     p.add_argument("--pad", action="store_true")
     p.add_argument("--bytes_per_oligo", type=int, default=18)
+    # extensions
+    p.add_argument("--list_ops", choices=["host", "device"], default="host", help="the filter as a Python loop, or on the GPU; same tallies")
+    p.add_argument("--device", type=int, default=0)
     return p
 
 
@@ -38,7 +41,7 @@ def main(argv=None, out=sys.stdout):
         conv_input_list = [s.rstrip("\n") for s in f.readlines()]
     print("num_oligos", len(conv_input_list), file=out)
     t = helper.tally_decoded_lists([lst for _, lst in read_lists(a.decoded_lists_dir)], conv_input_list, a.bytes_per_oligo,
-                                   a.pad, a.list_size)
+                                   a.pad, a.list_size, device=a.device if a.list_ops == "device" else None)
     for k in ("num_reads", "num_correct", "num_erasure_CRC_index", "num_error_CRC_index"):
         print(k + ":", t[k], file=out)
     return t

@@ -25,6 +25,7 @@
 #include "lva_kernels.h"
 #include "bc_kernels.h"
 #include "tp_kernels.h"
+#include "ls_kernels.h"
 
 using namespace lva;
 
@@ -1398,6 +1399,134 @@ int lva_find_barcode_batch(lva_decoder* d, const char* bases, const uint32_t* tr
   if (e) { g_hip_error = hipGetErrorString((hipError_t)e); return LVA_ERR_HIP; }
   HIP_TRY(hipMemcpyAsync(out, d_res, sizeof(BcResult) * n, hipMemcpyDeviceToHost, d->stream));
   HIP_TRY(hipStreamSynchronize(d->stream));
+  return LVA_OK;
+}
+
+}  // extern "C"
+
+/* ---------------------------------------------------------------------------------------------
+ * the consumers of a decoded list (csrc/ls_kernels.hip).  Like the RS entry
+ * points they take a device ordinal, work on a stream of their own and leave every decoder's profile alone.
+ * ------------------------------------------------------------------------------------------- */
+namespace {
+
+struct LsStream {               // a stream for the length of one call
+  hipStream_t s = nullptr;
+  ~LsStream() { if (s) (void)hipStreamDestroy(s); }
+};
+
+int ls_open(int32_t device, LsStream* st) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return LVA_ERR_NO_DEVICE;
+  if (hipSetDevice(device) != hipSuccess) return LVA_ERR_NO_DEVICE;
+  HIP_TRY(hipStreamCreateWithFlags(&st->s, hipStreamNonBlocking));
+  return LVA_OK;
+}
+
+// msgs / counts of n reads: the shape every list consumer accepts
+bool ls_shape_ok(int32_t n_reads, int32_t list_size, uint32_t msg_len) {
+  if (n_reads < 0 || list_size < 1 || msg_len < 1 || msg_len > (uint32_t)kLsMaxMsgLen) return false;
+  return (uint64_t)n_reads * (uint64_t)list_size * (uint64_t)msg_len < (1ull << 31);
+}
+
+}  // namespace
+
+extern "C" {
+
+int lva_list_filter(int32_t device, const uint8_t* msgs, const int32_t* counts, int32_t n_reads, int32_t list_size,
+                    uint32_t msg_len, int32_t use_entries, int32_t bytes_per_oligo, int32_t num_oligos, int32_t pad,
+                    int32_t* out_index, int32_t* out_rank, uint8_t* out_payload) {
+  if (!msgs || !counts || !out_index || !out_rank || !out_payload) return LVA_ERR_ARG;
+  if (!ls_shape_ok(n_reads, list_size, msg_len) || use_entries < 0 || use_entries > list_size) return LVA_ERR_ARG;
+  if (bytes_per_oligo < 1 || num_oligos < 1 || num_oligos > 4096) return LVA_ERR_ARG;
+  if ((uint64_t)msg_len != 12ull + 8ull + 8ull * (uint64_t)bytes_per_oligo + (pad ? 1ull : 0ull)) return LVA_ERR_ARG;
+  if (n_reads == 0) return LVA_OK;
+  const int32_t use = use_entries ? use_entries : list_size;
+  LsStream st;
+  const int so = ls_open(device, &st);
+  if (so != LVA_OK) return so;
+  const size_t n = (size_t)n_reads, mb = n * (size_t)list_size * msg_len, pb = n * (size_t)bytes_per_oligo;
+  DevBlock blk;
+  blk.cap = DevBlock::pad(mb) + 3 * DevBlock::pad(4 * n) + DevBlock::pad(pb);
+  if (hipMalloc(reinterpret_cast<void**>(&blk.base), blk.cap) != hipSuccess) return LVA_ERR_NOMEM;
+  uint8_t* d_msgs = blk.take<uint8_t>(mb);               // 256-byte aligned and padded: whole dwords may be read
+  int32_t* d_counts = blk.take<int32_t>(n);
+  int32_t* d_index = blk.take<int32_t>(n);
+  int32_t* d_rank = blk.take<int32_t>(n);
+  uint8_t* d_pay = blk.take<uint8_t>(pb);
+  HIP_TRY(hipMemcpyAsync(d_msgs, msgs, mb, hipMemcpyHostToDevice, st.s));
+  HIP_TRY(hipMemcpyAsync(d_counts, counts, 4 * n, hipMemcpyHostToDevice, st.s));
+  const int e = launch_ls_filter(d_msgs, d_counts, n_reads, list_size, msg_len, use, bytes_per_oligo, num_oligos, pad, d_index,
+                                 d_rank, d_pay, st.s);
+  if (e) { g_hip_error = hipGetErrorString((hipError_t)e); (void)hipStreamSynchronize(st.s); return LVA_ERR_HIP; }
+  HIP_TRY(hipMemcpyAsync(out_index, d_index, 4 * n, hipMemcpyDeviceToHost, st.s));
+  HIP_TRY(hipMemcpyAsync(out_rank, d_rank, 4 * n, hipMemcpyDeviceToHost, st.s));
+  HIP_TRY(hipMemcpyAsync(out_payload, d_pay, pb, hipMemcpyDeviceToHost, st.s));
+  HIP_TRY(hipStreamSynchronize(st.s));
+  return LVA_OK;
+}
+
+int lva_list_consensus(int32_t device, const int32_t* index, const uint8_t* payload, int32_t n_reads, int32_t bytes_per_oligo,
+                       int32_t num_oligos, int32_t first_only, uint8_t* out_present, uint8_t* out_payload, int32_t* out_votes) {
+  if (!index || !payload || !out_present || !out_payload || !out_votes) return LVA_ERR_ARG;
+  if (n_reads < 0 || bytes_per_oligo < 1 || num_oligos < 1 || num_oligos > 4096) return LVA_ERR_ARG;
+  if ((uint64_t)n_reads * (uint64_t)bytes_per_oligo >= (1ull << 31)) return LVA_ERR_ARG;
+  for (int32_t i = 0; i < n_reads; ++i)
+    if (index[i] >= num_oligos) return LVA_ERR_ARG;      // (negative: the read passed no entry and has no vote)
+  if (n_reads == 0) return LVA_OK;
+  LsStream st;
+  const int so = ls_open(device, &st);
+  if (so != LVA_OK) return so;
+  const size_t n = (size_t)n_reads, no = (size_t)num_oligos, pb = n * (size_t)bytes_per_oligo, ob = no * (size_t)bytes_per_oligo;
+  DevBlock blk;
+  blk.cap = 2 * DevBlock::pad(4 * n) + DevBlock::pad(pb) + DevBlock::pad(4 * (no + 1)) + DevBlock::pad(no) + DevBlock::pad(ob) +
+            DevBlock::pad(4 * no);
+  if (hipMalloc(reinterpret_cast<void**>(&blk.base), blk.cap) != hipSuccess) return LVA_ERR_NOMEM;
+  int32_t* d_index = blk.take<int32_t>(n);
+  int32_t* d_order = blk.take<int32_t>(n);
+  uint8_t* d_pay = blk.take<uint8_t>(pb);
+  int32_t* d_bucket = blk.take<int32_t>(no + 1);
+  uint8_t* d_present = blk.take<uint8_t>(no);
+  uint8_t* d_out = blk.take<uint8_t>(ob);
+  int32_t* d_votes = blk.take<int32_t>(no);
+  HIP_TRY(hipMemcpyAsync(d_index, index, 4 * n, hipMemcpyHostToDevice, st.s));
+  HIP_TRY(hipMemcpyAsync(d_pay, payload, pb, hipMemcpyHostToDevice, st.s));
+  const int e = launch_ls_consensus(d_index, d_pay, n_reads, bytes_per_oligo, num_oligos, first_only ? 1 : 0, d_bucket, d_order,
+                                    d_present, d_out, d_votes, st.s);
+  if (e) { g_hip_error = hipGetErrorString((hipError_t)e); (void)hipStreamSynchronize(st.s); return LVA_ERR_HIP; }
+  HIP_TRY(hipMemcpyAsync(out_present, d_present, no, hipMemcpyDeviceToHost, st.s));
+  HIP_TRY(hipMemcpyAsync(out_payload, d_out, ob, hipMemcpyDeviceToHost, st.s));
+  HIP_TRY(hipMemcpyAsync(out_votes, d_votes, 4 * no, hipMemcpyDeviceToHost, st.s));
+  HIP_TRY(hipStreamSynchronize(st.s));
+  return LVA_OK;
+}
+
+int lva_list_stats(int32_t device, const uint8_t* msgs, const int32_t* counts, const uint8_t* truth, int32_t n_reads,
+                   int32_t list_size, uint32_t msg_len, lva_list_stat* out) {
+  static_assert(sizeof(lva_list_stat) == kLsStatFields * sizeof(int32_t), "ls_stats writes the fields of lva_list_stat in order");
+  if (!msgs || !counts || !truth || !out) return LVA_ERR_ARG;
+  if (!ls_shape_ok(n_reads, list_size, msg_len)) return LVA_ERR_ARG;
+  if (n_reads == 0) return LVA_OK;
+  LsStream st;
+  const int so = ls_open(device, &st);
+  if (so != LVA_OK) return so;
+  const size_t n = (size_t)n_reads, mb = n * (size_t)list_size * msg_len, tb = n * msg_len;
+  DevBlock blk;
+  blk.cap = DevBlock::pad(mb) + DevBlock::pad(4 * n) + DevBlock::pad(tb) + DevBlock::pad(8 * kLsPackWords * n) +
+            DevBlock::pad(4 * kLsStatFields * n);
+  if (hipMalloc(reinterpret_cast<void**>(&blk.base), blk.cap) != hipSuccess) return LVA_ERR_NOMEM;
+  uint8_t* d_msgs = blk.take<uint8_t>(mb);
+  int32_t* d_counts = blk.take<int32_t>(n);
+  uint8_t* d_truth = blk.take<uint8_t>(tb);
+  uint64_t* d_packed = blk.take<uint64_t>(kLsPackWords * n);
+  int32_t* d_out = blk.take<int32_t>(kLsStatFields * n);
+  HIP_TRY(hipMemcpyAsync(d_msgs, msgs, mb, hipMemcpyHostToDevice, st.s));
+  HIP_TRY(hipMemcpyAsync(d_counts, counts, 4 * n, hipMemcpyHostToDevice, st.s));
+  HIP_TRY(hipMemcpyAsync(d_truth, truth, tb, hipMemcpyHostToDevice, st.s));
+  const int e = launch_ls_stats(d_msgs, d_counts, d_truth, n_reads, list_size, msg_len, d_packed, d_out, st.s);
+  if (e) { g_hip_error = hipGetErrorString((hipError_t)e); (void)hipStreamSynchronize(st.s); return LVA_ERR_HIP; }
+  HIP_TRY(hipMemcpyAsync(out, d_out, 4 * kLsStatFields * n, hipMemcpyDeviceToHost, st.s));
+  HIP_TRY(hipStreamSynchronize(st.s));
   return LVA_OK;
 }
 

@@ -24,6 +24,7 @@ def build_parser():
     p.add_argument("--original_file", type=str, required=True)
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--device", type=int, default=0)
+    p.add_argument("--list_ops", choices=["host", "device"], default="host", help="filter and consensus as Python loops, or on the GPU; same output")
     return p
 
 
@@ -45,7 +46,8 @@ def main(argv=None, out=sys.stdout):
             if os.path.isfile(list_file):
                 with open(list_file) as f:
                     lists.append([ln.rstrip("\n") for ln in f.readlines()][:a.list_size])
-        data, passed = rs_code.decode_from_lists(lists, a.bytes_per_oligo, num_oligos_RS, num_oligos, pad=a.pad, device=a.device)
+        data, passed = rs_code.decode_from_lists(lists, a.bytes_per_oligo, num_oligos_RS, num_oligos, pad=a.pad, device=a.device,
+                                                 list_ops=a.list_ops)
         ok = passed > 0 and data[:data_file_size] == original     # no read passed the filter: the reference dies in MainDecoder
         num_successes += int(ok)
         print("Success" if ok else "Failure", file=out)

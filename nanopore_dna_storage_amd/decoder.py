@@ -180,6 +180,10 @@ class Decoder:
     def decode_packed(self, flat, off, rc=None):
         """decode() on a host buffer that is already in the C ABI's form: `flat` float32 [sum nblk, 40] (all reads
         back to back), `off` int64 [n+1] block offsets.  The host->device copy happens inside the call."""
+        return self._unpack(len(off) - 1, *self._decode_packed_dense(flat, off, rc))
+
+    def _decode_packed_dense(self, flat, off, rc=None):
+        """decode_packed's outputs as the C ABI fills them: msgs uint8 [n, list_size, msg_len], scores, counts"""
         n = len(off) - 1
         assert flat.dtype == np.float32 and flat.flags.c_contiguous and off.dtype == np.int64
         rcf = None if rc is None else np.ascontiguousarray(rc, dtype=np.uint8)
@@ -189,7 +193,17 @@ class Decoder:
                                       msgs.ctypes.data, scores.ctypes.data, counts.ctypes.data)
         if st != 0:
             raise LvaError(st, self._L.lva_last_hip_error().decode())
-        return self._unpack(n, msgs, scores, counts)
+        return msgs, scores, counts
+
+    def decode_payloads(self, posts, rc, bytes_per_oligo, num_oligos, pad=False):
+        """decode() followed by the CRC-8 / index filter (helper.decode_list_CRC_index, helper.py:371-388) on the arrays
+        the decode filled, without a list of strings in between (list_ops.filter_lists: csrc/ls_kernels.hip).
+        -> dict(index int32 [n] (-1: no entry passed), rank int32 [n], payload uint8 [n, bytes_per_oligo], counts int32 [n])"""
+        from . import list_ops
+        flat, off = self._pack(posts)
+        msgs, _, counts = self._decode_packed_dense(flat, off, rc)
+        index, rank, payload = list_ops.filter_lists(msgs, counts, bytes_per_oligo, num_oligos, pad=pad, device=self.device)
+        return dict(index=index, rank=rank, payload=payload, counts=counts)
 
     # --- inputs resident in HBM (bench.py) ---------------------------------------------------
     def upload(self, posts):

@@ -204,7 +204,8 @@ def encode(data_file, oligo_file, bytes_per_oligo, RS_redundancy, conv_m, conv_r
 
 def simulate_and_decode(oligo_file, decoded_data_file, num_reads, data_file_size, bytes_per_oligo, RS_redundancy, conv_m, conv_r,
                         pad=False, syn_sub_prob=0.005, syn_del_prob=0.005, syn_ins_prob=0.0005, deepsimdwell=False, num_thr=16,
-                        list_size=1, seed=None, margin=6.0, device=0, out=None, decoder=None, posterior_source="softmax"):
+                        list_size=1, seed=None, margin=6.0, device=0, out=None, decoder=None, posterior_source="softmax",
+                        list_ops="host"):
     """helper.py:275-350, same arguments: num_reads times pick a random oligo and orientation, pass it through the
     substitution / deletion / insertion channel, turn it into a posterior matrix, decode a list of list_size candidates,
     take the first candidate whose CRC-8 checks and whose index is in range (the first payload seen for an index stands,
@@ -215,6 +216,8 @@ def simulate_and_decode(oligo_file, decoded_data_file, num_reads, data_file_size
     posterior_source: "softmax" -- every block's posteriors are the log-softmax of independent logits; "crf" -- what a
     flip-flop CRF network gives: transition scores (synth.scores_from_bases) that go through Decoder.decode_from_scores,
     forward-backward posteriors and decode without leaving the device.
+    list_ops: "host" -- the filter and the first-seen rule as the Python loops below; "device" -- the same on the GPU
+    (list_ops.filter_lists, list_ops.consensus with first_only), same counts and bytes.
     -> dict(num_attempted, num_success, num_unique, decoded bytes)."""
     import sys
     from . import rs_code, synth
@@ -245,8 +248,17 @@ def simulate_and_decode(oligo_file, decoded_data_file, num_reads, data_file_size
     finally:
         if own:
             dec.close()
+    if list_ops not in ("host", "device"):
+        raise ValueError("list_ops: 'host' or 'device'")
     decoded_dict = {}
     num_success = 0
+    if list_ops == "device":
+        from . import list_ops as lo
+        msgs, counts = lo.results_to_array(results, dec.list_size, msg_len)
+        index, _, payload = lo.filter_lists(msgs, counts, bytes_per_oligo, num_oligos, pad=pad, device=device)
+        num_success = int((index >= 0).sum())
+        decoded_dict = dict((k, v) for k, v in lo.consensus(index, payload, num_oligos, first_only=True, device=device))
+        results = []
     for res in results:
         if isinstance(res, (int, np.integer)):
             continue                                   # (the reference decoder aborts on such a read: no list)
@@ -291,11 +303,28 @@ def levenshtein(a, b):
     return prev[-1]
 
 
-def tally_decoded_lists(lists, conv_input_list, bytes_per_oligo, pad, list_size):
+def tally_decoded_lists(lists, conv_input_list, bytes_per_oligo, pad, list_size, device=None):
     """compute_error_rate_from_decoded_lists.py:18-56 over in-memory lists:
-    -> dict(num_reads, num_correct, num_erasure_CRC_index, num_error_CRC_index)"""
+    -> dict(num_reads, num_correct, num_erasure_CRC_index, num_error_CRC_index)
+    device: None -- the Python loop below; a GPU ordinal -- the filter on that device (list_ops.filter_lists), the
+    comparison with the encoder's input from its rank and index with numpy.  Same tallies."""
     num_oligos = len(conv_input_list)
     out = dict(num_reads=0, num_correct=0, num_erasure_CRC_index=0, num_error_CRC_index=0)
+    if device is not None:
+        from . import list_ops as lo
+        lists = [lst[:list_size] for lst in lists]
+        msg_len = index_len + crc_len + 8 * bytes_per_oligo + int(bool(pad))
+        msgs, counts = lo.lists_to_array(lists, msg_len=msg_len)
+        index, rank, _ = lo.filter_lists(msgs, counts, bytes_per_oligo, num_oligos, pad=pad, device=device)
+        hit = np.nonzero(index >= 0)[0]
+        sent = np.full((num_oligos, msg_len), 2, np.uint8)          # (2: equals no bit -- an input line of another length)
+        for k, line in enumerate(conv_input_list):
+            if len(line) == msg_len:
+                sent[k] = lo.bits_of(line)
+        correct = (msgs[hit, rank[hit]] == sent[index[hit]]).all(axis=1)
+        out.update(num_reads=len(lists), num_correct=int(correct.sum()), num_erasure_CRC_index=len(lists) - len(hit),
+                   num_error_CRC_index=len(hit) - int(correct.sum()))
+        return out
     for lst in lists:
         out["num_reads"] += 1
         index, _, msg = decode_list_CRC_index(lst[:list_size], bytes_per_oligo, num_oligos, pad)

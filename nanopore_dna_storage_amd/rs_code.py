@@ -96,10 +96,26 @@ def consensus(decoded):
     return [[k, d[k][0][0]] for k in d]
 
 
-def decode_from_lists(lists, bytes_per_oligo, num_oligos_RS, num_oligos, pad=False, list_size=None, device=0):
+def decode_from_lists(lists, bytes_per_oligo, num_oligos_RS, num_oligos, pad=False, list_size=None, device=0, list_ops="host"):
     """One trial of decode_RS_from_decoded_lists.py:30-55 on in-memory decoded lists (one list of '0'/'1' strings per
     read, best first): CRC-8/index filter per read (helper.decode_list_CRC_index), per-index consensus, RS decode.
+    list_ops: "host" -- filter and consensus as Python loops; "device" -- on the GPU (list_ops.filter_lists,
+    list_ops.consensus), same result.
     -> (data bytes = the decoded payloads joined, number of reads that passed the filter)"""
+    if list_ops not in ("host", "device"):
+        raise ValueError("list_ops: 'host' or 'device'")
+    if list_ops == "device":
+        from . import list_ops as lo
+        if not lists:
+            return b"", 0
+        msg_len = helper.index_len + helper.crc_len + 8 * bytes_per_oligo + int(bool(pad))
+        msgs, counts = lo.lists_to_array(lists if list_size is None else [lst[:list_size] for lst in lists], msg_len=msg_len)
+        index, _, payload = lo.filter_lists(msgs, counts, bytes_per_oligo, num_oligos, pad=pad, device=device)
+        passed = int((index >= 0).sum())
+        if not passed:
+            return b"", 0
+        rs_out = MainDecoder(lo.consensus(index, payload, num_oligos, device=device), num_oligos_RS, num_oligos, device=device)
+        return b"".join(rs_out), passed
     decoded = []
     for lst in lists:
         index, payload, _ = helper.decode_list_CRC_index(lst if list_size is None else lst[:list_size], bytes_per_oligo, num_oligos, pad)

@@ -34,6 +34,8 @@ def build_parser():
     p.add_argument("--margin", type=float, default=6.0)
     p.add_argument("--max_deviation", type=int, default=20)
     p.add_argument("--device", type=int, default=0)
+    p.add_argument("--stats", choices=["host", "device"], default="host",
+                   help="where the per-trial statistics are computed: Python loops, or the GPU (list_ops.list_stats); same output")
     return p
 
 
@@ -53,7 +55,12 @@ def run(args, out=sys.stdout, decoder=None):
             decoder.close()
     top, lst, ham, ham8, ham16, edit = [], [], [], [], [], []
     n = args.msg_len
-    for rd, res in zip(reads, results):
+    dev = None
+    if getattr(args, "stats", "host") == "device" and reads and not any(isinstance(res, int) or not len(res[0]) for res in results):
+        from . import list_ops
+        msgs, counts = list_ops.results_to_array(results, max(len(res[0]) for res in results), n)
+        dev = list_ops.list_stats(msgs, counts, np.array([rd["msg"] for rd in reads], dtype=np.uint8), device=args.device)
+    for t, (rd, res) in enumerate(zip(reads, results)):
         msg = "".join(map(str, rd["msg"]))
         print(msg, file=out)
         print("len(seq):", len(bases_to_str(rd["oligo"])), file=out)
@@ -63,17 +70,26 @@ def run(args, out=sys.stdout, decoder=None):
         print("Top message:", file=out)
         print(decoded[0], file=out)
         print("List size:", len(decoded), file=out)
-        top.append(decoded[0] == msg)
-        lst.append(msg in decoded)
+        if dev is not None:
+            top.append(bool(dev["top_correct"][t]))
+            lst.append(bool(dev["list_correct"][t]))
+        else:
+            top.append(decoded[0] == msg)
+            lst.append(msg in decoded)
         print("Top correct:", top[-1], file=out)
         print("List correct:", lst[-1], file=out)
-        ham.append(helper.hamming(msg, decoded[0]))
-        ham8.append(sum(decoded[0][i * 8:(i + 1) * 8] != msg[i * 8:(i + 1) * 8] for i in range(math.ceil(n / 8))))
-        ham16.append(sum(decoded[0][i * 16:(i + 1) * 16] != msg[i * 16:(i + 1) * 16] for i in range(math.ceil(n / 16))))
+        if dev is not None:
+            ham.append(int(dev["hamming"][t]))
+            ham8.append(int(dev["hamming8"][t]))
+            ham16.append(int(dev["hamming16"][t]))
+        else:
+            ham.append(helper.hamming(msg, decoded[0]))
+            ham8.append(sum(decoded[0][i * 8:(i + 1) * 8] != msg[i * 8:(i + 1) * 8] for i in range(math.ceil(n / 8))))
+            ham16.append(sum(decoded[0][i * 16:(i + 1) * 16] != msg[i * 16:(i + 1) * 16] for i in range(math.ceil(n / 16))))
         print("Hamming distance of top:", ham[-1], file=out)
         print("Hamming distance of top (8 blocks):", ham8[-1], file=out)
         print("Hamming distance of top (16 blocks):", ham16[-1], file=out)
-        edit.append(helper.levenshtein(msg, decoded[0]))
+        edit.append(int(dev["edit"][t]) if dev is not None else helper.levenshtein(msg, decoded[0]))
         print("Edit distance", edit[-1], file=out)
         if not top[-1]:
             print("Error pattern (original, errors):", file=out)
