@@ -59,6 +59,58 @@ def test_three_blocks_equal_brute_force():
     assert np.abs(T.posteriors_flappie_f32(x) - want).max() < 1e-5
 
 
+def _scaled_worst(nblk, spread, largest):
+    return (2 * nblk + 24) * _ulp32(2 * (2 * spread + 2 * np.log(8)) + largest)
+
+
+def _scaled_case(nblk, reads):
+    rng = np.random.default_rng(900 + nblk)
+    xs = [rng.uniform(-5, 5, (nblk, 40)).astype(np.float32) for _ in range(reads)]
+    a, c = T.posteriors_f64_batch(xs), T.posteriors_scaled_f32_batch(xs)
+    assert all(y.dtype == np.float32 and y.shape == x.shape for x, y in zip(xs, c))
+    return max(float(np.abs(y.astype(np.float64) - z).max()) for y, z in zip(c, a))
+
+
+def test_scaled_f32_stays_at_float32_rounding_at_every_length():
+    """The rescaled float32 order against float64 at 1, 3, 33, 400 and 3000 blocks of uniform +-5 scores.  With scores of
+    spread D, every flip entry of a new vector lies within D + ln 8 of the largest (all eight states lead into every flip, and
+    every state leads into all four flips); a flop entry is reached from one flip and itself, so it lies at most one more
+    step's D + ln 8 and D below.  A rescaled vector therefore stays within [-(2 D + 2 ln 8), 0] at any length, and a
+    posterior candidate -- forward + backward + score -- below M = 2 (2 D + 2 ln 8) + max |score|.  Every step rounds about
+    four times at that magnitude, the 40-entry normalisation 40 times more: the worst case of the flappie test with M
+    constant.  That bound still counts every step's rounding as if all added up; what rescaling is for is that they do not:
+    the error of 3000 blocks is held to twice that of 33."""
+    sizes = {1: 512, 3: 256, 33: 256, 400: 32, 3000: 8}
+    err = {n: _scaled_case(n, r) for n, r in sizes.items()}
+    for n, e in err.items():
+        bound = _scaled_worst(n, 10, 5)
+        print("nblk %d: |scaled_f32 - f64| = %.3g, worst case %.3g" % (n, e, bound))
+        assert e <= bound
+    assert err[3000] <= 2 * err[33]
+
+
+@pytest.mark.parametrize("nblk", [1, 2, 3])
+def test_scaled_f32_equals_brute_force(nblk):
+    """every state sequence enumerated; the float32 distance within the worst case of the test above for these scores"""
+    x = np.random.default_rng(40 + nblk).normal(0, 2, (nblk, 40)).astype(np.float32)
+    want = T.brute_force(x)
+    assert np.abs(T.posteriors_f64(x) - want).max() < 1e-12
+    bound = _scaled_worst(nblk, float(x.max() - x.min()), float(np.abs(x).max()))
+    got = T.posteriors_scaled_f32(x)
+    assert got.dtype == np.float32 and np.abs(got - want).max() <= bound
+
+
+def test_scaled_f32_batch_equals_single():
+    rng = np.random.default_rng(31)
+    xs = [rng.normal(0, 2, (n, 40)).astype(np.float32) for n in (5, 0, 9, 1, 34, 2, 0)]
+    got = T.posteriors_scaled_f32_batch(xs)
+    for x, c in zip(xs, got):
+        assert c.shape == x.shape and c.dtype == np.float32
+        if len(x):
+            assert np.array_equal(c, T.posteriors_scaled_f32(x))
+    assert T.posteriors_scaled_f32_batch([]) == []
+
+
 def test_argmax_follows_the_true_path():
     for seed in (1, 2, 3):
         x = synth.make_read_scores(6, 1, 60, seed, margin=6.0)

@@ -10,8 +10,14 @@ state s into flip b; index 32+s goes into flop: from flip s to flop s+4 for s < 
                           vectors (they grow by about 5 per block), the 40 entries of a block summed one after the other.
                           What a float32 implementation of the textbook order loses against float64: the error the GPU
                           kernels are measured against.
+  posteriors_scaled_f32   the same order, the same pairwise folds and the same 40-entry normalisation in np.float32, with the
+                          textbook per-step rescaling: the maximum of the previous forward (backward) vector is taken off it
+                          before each forward (backward) step -- a constant per block that the normalisation removes -- so the
+                          values stay those of a few scores and the error does not grow with the read.  The tight yardstick
+                          for long reads.  It is not a restatement of the kernels (those take the maximum of the candidates,
+                          one expf per candidate and one logf per state); it must not become one.
 
-Both work on a batch: a list of [nblk_i, 40] arrays, processed together (one numpy operation per step for all reads).
+All work on a batch: a list of [nblk_i, 40] arrays, processed together (one numpy operation per step for all reads).
 """
 import numpy as np
 
@@ -115,6 +121,52 @@ def posteriors_flappie_f32_batch(scores):
 
 def posteriors_flappie_f32(scores):
     return posteriors_flappie_f32_batch([scores])[0]
+
+
+def posteriors_scaled_f32_batch(scores):
+    f = np.float32
+    x, lens = _stack(scores, f)
+    R, n, _ = x.shape
+    with np.errstate(all="ignore"):
+        fwd = np.zeros((R, n, 8), f)                                 # the rescaled vector before block t
+        cur = np.zeros((R, 8), f)
+        for t in range(n):
+            prev = (cur - cur.max(axis=1, keepdims=True)).astype(f)
+            fwd[:, t] = prev
+            cur = np.empty((R, 8), f)
+            cur[:, 4:] = _lse32((prev[:, 4:] + x[:, t, 36:40]).astype(f), (prev[:, :4] + x[:, t, 32:36]).astype(f))
+            tf = x[:, t, :32].reshape(R, 4, 8)
+            acc = (tf[:, :, 0] + prev[:, None, 0]).astype(f)
+            for s in range(1, 8):
+                acc = _lse32(acc, (tf[:, :, s] + prev[:, None, s]).astype(f))
+            cur[:, :4] = acc
+        post = np.zeros_like(x)
+        back = np.zeros((R, 8), f)
+        for t in range(n, 0, -1):
+            back = np.where((t < lens)[:, None], back, f(0))
+            back = (back - back.max(axis=1, keepdims=True)).astype(f)
+            xt = x[:, t - 1]
+            a = fwd[:, t - 1]
+            tp = np.empty((R, 40), f)
+            tp[:, :32] = ((a[:, None, :] + back[:, :4, None]).astype(f) + xt[:, :32].reshape(R, 4, 8)).astype(f).reshape(R, 32)
+            tp[:, 36:40] = ((a[:, 4:] + back[:, 4:]).astype(f) + xt[:, 36:40]).astype(f)
+            tp[:, 32:36] = ((a[:, :4] + back[:, 4:]).astype(f) + xt[:, 32:36]).astype(f)
+            cur = np.empty((R, 8), f)
+            cur[:, 4:] = (back[:, 4:] + xt[:, 36:40]).astype(f)
+            cur[:, :4] = (back[:, 4:] + xt[:, 32:36]).astype(f)
+            for b in range(4):
+                cur = _lse32(cur, (xt[:, b * 8:b * 8 + 8] + back[:, b, None]).astype(f))
+            back = cur
+            post[:, t - 1] = tp
+        tot = post[:, :, 0].copy()
+        for i in range(1, 40):
+            tot = _lse32(tot, post[:, :, i])
+        post = (post - tot[:, :, None]).astype(f)
+    return _unstack(post, lens)
+
+
+def posteriors_scaled_f32(scores):
+    return posteriors_scaled_f32_batch([scores])[0]
 
 
 def brute_force(scores):
