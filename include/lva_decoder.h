@@ -106,7 +106,8 @@ typedef struct lva_profile {
 const char *lva_version(void);
 /* LVA_ABI_VERSION of the library that was loaded.  It changes whenever a struct of this header changes size or layout
  * (5: lva_profile gained overflow_steps and working_bytes): a caller built against another value must not pass structs.
- * Entry points added since (lva_stream_*, lva_transpost_*, lva_device_download) change no struct and keep it at 5. */
+ * Entry points added since (lva_stream_*, lva_transpost_*, lva_device_download, lva_list_*, lva_demux_*) change no struct
+ * and keep it at 5. */
 #define LVA_ABI_VERSION 5
 int lva_abi_version(void);
 const char *lva_strerror(int code);
@@ -187,7 +188,7 @@ int lva_decoder_set_launch_events(lva_decoder *d, int32_t on);
  * in flight, results come out as they finish.  A read's list and scores are those of lva_decode_batch, bit for bit,
  * whenever it was submitted and whatever else is in flight.  The library starts no thread: lva_stream_poll drives the
  * stream.  One stream per decoder; while it is open every batch entry point of that decoder (lva_decode_*, lva_basecall_*,
- * lva_locate_payload_*, lva_find_barcode_batch) returns LVA_ERR_BUSY.
+ * lva_locate_payload_*, lva_find_barcode_batch, lva_demux_*) returns LVA_ERR_BUSY.
  * replaces: the process per read of helper.py:305, simulator.py:85 and generate_decoded_lists.py:90, and the side-by-side
  * driver copies the reference scales with (util/extra/generate_read_id_files.py:23-36, merge_lists.py:11-21). */
 typedef struct lva_stream lva_stream;
@@ -296,6 +297,57 @@ int lva_locate_payload_batch(lva_decoder *d, const float *post, const int64_t *r
 int lva_locate_payload_batch_device(lva_decoder *d, const float *post_dev, const int64_t *row_offsets, int32_t n_reads,
                                     const char *start_barcode, const char *end_barcode, uint32_t min_len,
                                     lva_payload_pos *out);
+
+/* ---------------------------------------------------------------------------------------------
+ * DESIGN.md section 1 row N3': demultiplexing a pooled run.  The reference's real data is ONE sequencing run of
+ * thirteen experiments, each with its own barcode pair and its own code (the table of encode_experiments.py:3-33, used at
+ * :117-128); it sorts the pooled reads with an aligner (util/align_compute_stats.sh + util/generate_read_id_file.py) and
+ * then runs generate_decoded_lists.py:68-79 once per experiment.  Here a read is basecalled once, its basecall is searched
+ * for every experiment's barcodes in one launch, and one decision per read names the experiment, the orientation and the
+ * payload window; the caller decodes each group with its own code from the same resident buffer
+ * (lva_decode_windows_device).
+ *
+ * For every experiment e the candidate is what lva_locate_payload_batch gives for (start_barcode, end_barcode, min_len) of
+ * exps[e].  A candidate is located when start_pos != -1; its total is dist_start + dist_end.  The located candidate with the
+ * smallest total wins (the lowest e on a draw); the runner-up is the located candidate with the smallest total among the
+ * OTHER experiments (runner_up = -1, runner_up_dist = INT32_MAX when there is none).  reason is the first that applies:
+ *   1  no candidate is located            (experiment = -1, pos = {-1, -1, INT32_MAX, INT32_MAX, 0, 0})
+ *   2  max_dist >= 0 and total > max_dist
+ *   3  runner_up_dist - total < min_margin (a missing runner-up never is too close)
+ *   4  the winner's window is shorter than its min_len (the candidate's ok is 0)
+ *   0  none: the read is assigned
+ * and in cases 0, 2, 3, 4 pos is the winner's candidate with ok = (reason == 0).
+ * 1 <= n_exps <= 64; barcodes of 1..64 characters out of ACGTN (an N, in a barcode or in a basecall, matches nothing);
+ * min_margin >= 0; otherwise LVA_ERR_ARG before the device is touched.  n_reads = 0 succeeds and touches nothing.  Read
+ * limits, LVA_ERR_BUSY and "complete on return" as for lva_locate_payload_batch.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct lva_experiment_barcodes {
+  const char *start_barcode, *end_barcode;
+  uint32_t min_len;             /* MEM_CONV + MSG_LEN + 1 of the experiment's code (generate_decoded_lists.py:76) */
+} lva_experiment_barcodes;
+
+typedef struct lva_demux_pos {
+  lva_payload_pos pos;
+  int32_t experiment;           /* the winner, -1 when nothing is located */
+  int32_t reason;               /* 0: assigned; 1..4 above */
+  int32_t runner_up, runner_up_dist;
+} lva_demux_pos;
+
+/* replaces: util/align_compute_stats.sh + util/generate_read_id_file.py (the reference's sorting step) and
+ * generate_decoded_lists.py:68-79 per experiment of encode_experiments.py:3-33.
+ * all_out: [n_reads][n_exps] candidates, may be NULL. */
+int lva_demux_batch(lva_decoder *d, const float *post, const int64_t *row_offsets, int32_t n_reads,
+                    const lva_experiment_barcodes *exps, int32_t n_exps, int32_t max_dist /* < 0: none */,
+                    int32_t min_margin, lva_demux_pos *out, lva_payload_pos *all_out);
+/* Same with the posteriors resident on the decoder's device (lva_device_alloc / lva_transpost_batch_device). */
+int lva_demux_batch_device(lva_decoder *d, const float *post_dev, const int64_t *row_offsets, int32_t n_reads,
+                           const lva_experiment_barcodes *exps, int32_t n_exps, int32_t max_dist, int32_t min_margin,
+                           lva_demux_pos *out, lva_payload_pos *all_out);
+/* Same on given basecalls (bases / trans / base_offsets as for lva_find_barcode_batch), both orientations.
+ * replaces: helper.find_barcode_pos_in_post (helper.py:157-210) twice per experiment + generate_decoded_lists.py:68-79. */
+int lva_demux_bases_batch(lva_decoder *d, const char *bases, const uint32_t *trans, const int64_t *base_offsets,
+                          int32_t n_reads, const lva_experiment_barcodes *exps, int32_t n_exps, int32_t max_dist,
+                          int32_t min_margin, lva_demux_pos *out, lva_payload_pos *all_out);
 
 /* ---------------------------------------------------------------------------------------------
  * the Reed-Solomon outer code, RS(65535, 65535 - redundancy) over GF(2^16)

@@ -29,6 +29,7 @@ EXPORTS = [
     "lva_stream_open", "lva_stream_close", "lva_stream_submit", "lva_stream_poll", "lva_stream_pending",
     "lva_transpost_batch", "lva_transpost_batch_device", "lva_device_download",
     "lva_list_filter", "lva_list_consensus", "lva_list_stats",
+    "lva_demux_batch", "lva_demux_batch_device", "lva_demux_bases_batch",
 ]
 
 
@@ -75,6 +76,15 @@ class Profile(ctypes.Structure):
 class PayloadPos(ctypes.Structure):
     _fields_ = [("start_pos", ctypes.c_int32), ("end_pos", ctypes.c_int32), ("dist_start", ctypes.c_int32),
                 ("dist_end", ctypes.c_int32), ("rc", ctypes.c_int32), ("ok", ctypes.c_int32)]
+
+
+class ExperimentBarcodes(ctypes.Structure):
+    _fields_ = [("start_barcode", ctypes.c_char_p), ("end_barcode", ctypes.c_char_p), ("min_len", ctypes.c_uint32)]
+
+
+class DemuxPos(ctypes.Structure):
+    _fields_ = [("pos", PayloadPos), ("experiment", ctypes.c_int32), ("reason", ctypes.c_int32),
+                ("runner_up", ctypes.c_int32), ("runner_up_dist", ctypes.c_int32)]
 
 
 class ListStat(ctypes.Structure):
@@ -163,5 +173,11 @@ def load_library():
     L.lva_list_filter.argtypes = [i32, vp, vp, i32, i32, u32, i32, i32, i32, i32, vp, vp, vp]
     L.lva_list_consensus.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.lva_list_stats.argtypes = [i32, vp, vp, vp, i32, i32, u32, vp]
+    for name in ("lva_demux_batch", "lva_demux_batch_device", "lva_demux_bases_batch"):
+        if not hasattr(L, name):                     # additive again: same ABI version
+            raise ImportError("%s has no demultiplexing (%s): rebuild it" % (path, name))
+    L.lva_demux_batch.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp]
+    L.lva_demux_batch_device.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp]
+    L.lva_demux_bases_batch.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, i32, vp, vp]
     _lib = L
     return L

@@ -201,22 +201,20 @@ __global__ __launch_bounds__(256) void bc_search(const char* __restrict__ bases,
   }
 }
 
-__global__ void bc_finalize(const uint32_t* __restrict__ trans, const int64_t* __restrict__ base_off,
-                            const int32_t* __restrict__ nbases, int32_t n_reads, BcPatterns pat, int n_orient,
-                            uint32_t min_len, const uint32_t* __restrict__ best, BcResult* __restrict__ out) {
-  const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n_reads) return;
-  const int32_t n = nbases[r];
-  const uint32_t* tr = trans + base_off[r];
+// The candidate of one barcode pair for one read: positions in the posterior matrix (helper.py:192-210), orientation
+// choice and length check of generate_decoded_lists.py:68-79.  best4 / len4: the four search results and pattern lengths
+// of the pair in the order of BcPatterns.  Shared by bc_finalize and bc_demux_finalize.
+__device__ __forceinline__ BcResult bc_candidate(const uint32_t* __restrict__ tr, int32_t n, const uint32_t* __restrict__ best4,
+                                                 const uint8_t* __restrict__ len4, int n_orient, uint32_t min_len) {
   int32_t sp[2], ep[2], ds[2], de[2];
   for (int o = 0; o < 2; ++o) {
     sp[o] = -1; ep[o] = -1; ds[o] = kBcInf; de[o] = kBcInf;
     if (o >= n_orient) continue;
-    const uint32_t ks = best[r * 4 + 2 * o], ke = best[r * 4 + 2 * o + 1];
+    const uint32_t ks = best4[2 * o], ke = best4[2 * o + 1];
     if (ks == kBcNone || ke == kBcNone) continue;        // too short a read (:177-179) or an empty search range
     const int32_t s_first = (int32_t)(ks & 0xFFFFFu);
     const int32_t e_first = n / 2 + (int32_t)(ke & 0xFFFFFu);
-    const int32_t s_last = s_first + pat.len[2 * o] - 1;
+    const int32_t s_last = s_first + len4[2 * o] - 1;
     const int32_t a = (int32_t)tr[s_last + 1] - 1;       // :193
     const int32_t b = (int32_t)tr[e_first - 1] - 1;      // :194
     if (b < a) continue;                                 // "Barcode removal failure" :206-208
@@ -229,6 +227,161 @@ __global__ void bc_finalize(const uint32_t* __restrict__ trans, const int64_t* _
   res.dist_end = de[rc] == kBcInf ? 0x7FFFFFFF : de[rc];
   res.rc = rc;
   res.ok = !(sp[rc] == -1 || (uint32_t)(ep[rc] - sp[rc] + 1) < min_len) ? 1 : 0;   // :76
+  return res;
+}
+
+__global__ void bc_finalize(const uint32_t* __restrict__ trans, const int64_t* __restrict__ base_off,
+                            const int32_t* __restrict__ nbases, int32_t n_reads, BcPatterns pat, int n_orient,
+                            uint32_t min_len, const uint32_t* __restrict__ best, BcResult* __restrict__ out) {
+  const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_reads) return;
+  out[r] = bc_candidate(trans + base_off[r], nbases[r], best + (size_t)r * 4, pat.len, n_orient, min_len);
+}
+
+// ---------------------------------------------------------------------------------------------
+// DESIGN.md section 1 row N3': a pooled run.  K experiments, each with its own barcode pair, share one sequencing run
+// (the table of encode_experiments.py:3-33); the reference sorts the reads with an aligner, here every read's one
+// basecall is searched for every experiment's barcodes in one launch and one thread per read decides.
+//
+// bc_search_multi: grid x = read, y = half (0: the start barcodes of both orientations, searched in the first half of
+// the basecall; 1: the end barcodes, second half); 256 threads = 256 windows at a time.  A thread packs the up-to-64
+// characters of its window into registers once (2 bits per base and a validity bit: a character outside ACGT matches
+// nothing, as in bc_search) and runs bc_search's recurrence on them against each of the 2K patterns of its half, whose
+// peq masks sit in LDS.  Per pattern the keys of a wavefront are reduced in registers and lane 0 folds the result into the
+// pattern's LDS word with a minimum, which does not depend on the order: (distance << 20 | window index - lo), as bc_search.
+// ---------------------------------------------------------------------------------------------
+constexpr int kBcMultiHalf = 2 * kMaxExperiments;      // patterns of one half
+
+__global__ __launch_bounds__(256) void bc_search_multi(const char* __restrict__ bases, const int64_t* __restrict__ base_off,
+                                                       const int32_t* __restrict__ nbases, const BcPatterns* __restrict__ pats,
+                                                       int32_t n_exps, uint32_t* __restrict__ best) {
+  __shared__ unsigned long long s_peq[kBcMultiHalf][4];  // bit i of s_peq[j][b]: character i of pattern j is base b
+  __shared__ uint32_t s_best[kBcMultiHalf];
+  __shared__ int32_t s_hi[kBcMultiHalf];                 // windows [lo, s_hi[j]) of pattern j; lo is the half's
+  __shared__ int32_t s_len[kBcMultiHalf];
+  __shared__ int32_t s_hi_max, s_len_max;
+  const uint32_t r = blockIdx.x, half = blockIdx.y, tid = threadIdx.x;
+  const int32_t np = 2 * n_exps;                         // pattern j of the half: experiment j >> 1, orientation j & 1
+  const int32_t n = nbases[r];
+  const int32_t lo = half ? n / 2 : 0;                   // helper.py:181,185
+  const char* txt = bases + base_off[r];
+  if (tid == 0) { s_hi_max = lo; s_len_max = 0; }
+  __syncthreads();
+  for (int32_t q = (int32_t)tid; q < np * 4; q += 256) {
+    const int32_t j = q >> 2, b = q & 3;
+    const BcPatterns& p = pats[j >> 1];
+    const int32_t w = 2 * (j & 1) + (int32_t)half, m = p.len[w];
+    unsigned long long mask = 0;
+    for (int32_t i = 0; i < m; ++i) mask |= (unsigned long long)(p.pat[w][i] == "ACGT"[b]) << i;
+    s_peq[j][b] = mask;
+    if (b == 0) {
+      const int32_t ls = p.len[w & 2], le = p.len[(w & 2) + 1];
+      int32_t hi = lo;
+      if (ls + le <= n) hi = half ? n - le : n / 2 + 1 - ls;                  // :177-179, :181, :185
+      hi = hi < lo ? lo : hi;
+      s_hi[j] = hi; s_len[j] = m; s_best[j] = kBcNone;
+      atomicMax(&s_hi_max, hi);
+      if (hi > lo) atomicMax(&s_len_max, m);
+    }
+  }
+  __syncthreads();
+  const int32_t hi_max = s_hi_max, len_max = s_len_max;
+  for (int32_t i0 = lo; i0 < hi_max; i0 += 256) {        // uniform: every wavefront makes the same passes
+    const int32_t i = i0 + (int32_t)tid;
+    // the window's characters, read once: 16 per word, 2 bits each (A 0, C 1, G 2, T 3); the index is clamped into the
+    // read (hi_max > lo implies n >= 2), no window that is searched reaches the clamp
+    uint32_t code[4] = {0u, 0u, 0u, 0u}, valid[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      if (16 * g < len_max) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+          int32_t at = i + 16 * g + k;
+          at = at < n ? at : n - 1;
+          const uint32_t ch = (uint32_t)(uint8_t)txt[at];
+          const uint32_t h2 = (ch >> 1) & 3u;            // A 0, C 1, G 3, T 2
+          code[g] |= (h2 ^ (h2 >> 1)) << (2 * k);
+          valid[g] |= (uint32_t)(ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T') << k;
+        }
+      }
+    }
+    for (int32_t j = 0; j < np; ++j) {
+      const bool mine = i < s_hi[j];
+      if (!__any(mine)) continue;
+      const int32_t m = s_len[j];
+      const unsigned long long peq0 = s_peq[j][0], peq1 = s_peq[j][1], peq2 = s_peq[j][2], peq3 = s_peq[j][3];
+      const unsigned long long top = 1ull << (m - 1);
+      // unit-cost edit distance of pattern j and txt[i .. i+m): the recurrence of bc_search
+      unsigned long long vp = ~0ull, vn = 0ull;
+      uint32_t score = (uint32_t)m;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        uint32_t cw = code[g], vw = valid[g];
+        const int32_t cnt = m - 16 * g < 16 ? m - 16 * g : 16;
+        for (int32_t k = 0; k < cnt; ++k) {
+          const unsigned long long sel = (cw & 2u) ? ((cw & 1u) ? peq3 : peq2) : ((cw & 1u) ? peq1 : peq0);
+          const unsigned long long eq = (vw & 1u) ? sel : 0ull;
+          cw >>= 2; vw >>= 1;
+          const unsigned long long x = eq | vn;
+          const unsigned long long d0 = ((vp + (x & vp)) ^ vp) | x;
+          const unsigned long long hn = vp & d0;
+          const unsigned long long hp = vn | ~(vp | d0);
+          score += (hp & top) ? 1u : 0u;
+          score -= (hn & top) ? 1u : 0u;
+          const unsigned long long xs = (hp << 1) | 1ull;
+          vn = xs & d0;
+          vp = (hn << 1) | ~(xs | d0);
+        }
+      }
+      uint32_t key = mine ? (score << 20) | (uint32_t)(i - lo) : kBcNone;    // smallest distance, then first index (:190-191)
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t other = __shfl_xor(key, o);
+        key = other < key ? other : key;
+      }
+      if ((tid & 63u) == 0 && key != kBcNone) atomicMin(&s_best[j], key);
+    }
+  }
+  __syncthreads();
+  for (int32_t j = (int32_t)tid; j < np; j += 256)
+    best[(size_t)r * 4 * n_exps + 4 * (j >> 1) + 2 * (j & 1) + half] = s_best[j];
+}
+
+// One thread per read: the candidate of every experiment (bc_candidate, what bc_finalize gives for that pair and that
+// min_len), then the choice.  A candidate is located when start_pos != -1, its total is dist_start + dist_end; the smallest
+// total wins (the lowest experiment on a draw), the runner-up is the best located candidate of the other experiments.
+// reason: 0 assigned, 1 nothing located, 2 total > max_dist (max_dist >= 0), 3 runner-up closer than min_margin,
+// 4 window shorter than the winner's min_len.
+__global__ void bc_demux_finalize(const uint32_t* __restrict__ trans, const int64_t* __restrict__ base_off,
+                                  const int32_t* __restrict__ nbases, int32_t n_reads, const BcPatterns* __restrict__ pats,
+                                  const uint32_t* __restrict__ min_len, int32_t n_exps, int32_t max_dist, int32_t min_margin,
+                                  const uint32_t* __restrict__ best, BcDemuxResult* __restrict__ out,
+                                  BcResult* __restrict__ all_out) {
+  const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_reads) return;
+  const int32_t n = nbases[r];
+  const uint32_t* tr = trans + base_off[r];
+  constexpr int32_t kNone = 0x7FFFFFFF;
+  int32_t t1 = kNone, i1 = -1, t2 = kNone, i2 = -1;
+  BcResult win;
+  win.start_pos = -1; win.end_pos = -1; win.dist_start = kNone; win.dist_end = kNone; win.rc = 0; win.ok = 0;
+  for (int32_t e = 0; e < n_exps; ++e) {
+    const BcResult c = bc_candidate(tr, n, best + ((size_t)r * n_exps + e) * 4, pats[e].len, 2, min_len[e]);
+    if (all_out) all_out[(size_t)r * n_exps + e] = c;
+    if (c.start_pos == -1) continue;
+    const int32_t tot = c.dist_start + c.dist_end;       // both below 2^20
+    if (i1 < 0 || tot < t1) { t2 = t1; i2 = i1; t1 = tot; i1 = e; win = c; }
+    else if (i2 < 0 || tot < t2) { t2 = tot; i2 = e; }
+  }
+  int32_t reason = 0;
+  if (i1 < 0) reason = 1;
+  else if (max_dist >= 0 && t1 > max_dist) reason = 2;
+  else if (i2 >= 0 && (long long)t2 - (long long)t1 < (long long)min_margin) reason = 3;
+  else if (!win.ok) reason = 4;
+  BcDemuxResult res;
+  res.pos = win;
+  res.pos.ok = reason == 0 ? 1 : 0;
+  res.experiment = i1; res.reason = reason; res.runner_up = i2; res.runner_up_dist = i2 < 0 ? kNone : t2;
   out[r] = res;
 }
 
@@ -254,6 +407,23 @@ int launch_bc_finalize(const uint32_t* trans, const int64_t* base_off, const int
   if (n_reads <= 0) return 0;
   hipLaunchKernelGGL(bc_finalize, dim3((n_reads + 63) / 64), dim3(64), 0, (hipStream_t)stream, trans, base_off, nbases,
                      n_reads, pat, n_orient, min_len, best, out);
+  return (int)hipGetLastError();
+}
+
+int launch_bc_search_multi(const char* bases, const int64_t* base_off, const int32_t* nbases, int32_t n_reads,
+                           const BcPatterns* pats, int32_t n_exps, uint32_t* best, void* stream) {
+  if (n_reads <= 0) return 0;
+  hipLaunchKernelGGL(bc_search_multi, dim3(n_reads, 2), dim3(256), 0, (hipStream_t)stream, bases, base_off, nbases, pats,
+                     n_exps, best);
+  return (int)hipGetLastError();
+}
+
+int launch_bc_demux_finalize(const uint32_t* trans, const int64_t* base_off, const int32_t* nbases, int32_t n_reads,
+                             const BcPatterns* pats, const uint32_t* min_len, int32_t n_exps, int32_t max_dist,
+                             int32_t min_margin, const uint32_t* best, BcDemuxResult* out, BcResult* all_out, void* stream) {
+  if (n_reads <= 0) return 0;
+  hipLaunchKernelGGL(bc_demux_finalize, dim3((n_reads + 63) / 64), dim3(64), 0, (hipStream_t)stream, trans, base_off, nbases,
+                     n_reads, pats, min_len, n_exps, max_dist, min_margin, best, out, all_out);
   return (int)hipGetLastError();
 }
 

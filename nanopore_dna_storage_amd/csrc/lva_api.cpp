@@ -1404,6 +1404,169 @@ int lva_find_barcode_batch(lva_decoder* d, const char* bases, const uint32_t* tr
 
 }  // extern "C"
 
+// ---------------------------------------------------------------------------------------------
+// DESIGN.md section 1 row N3': demultiplexing a pooled run (bc_search_multi, bc_demux_finalize).
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+struct DemuxArgs {
+  std::vector<BcPatterns> pats;
+  std::vector<uint32_t> min_len;
+  int32_t max_dist, min_margin;
+};
+
+// everything that can be refused without the device
+int demux_args(const lva_experiment_barcodes* exps, int32_t n_exps, int32_t max_dist, int32_t min_margin, DemuxArgs* a) {
+  if (!exps || n_exps < 1 || n_exps > kMaxExperiments || min_margin < 0) return LVA_ERR_ARG;
+  a->pats.resize(n_exps);
+  a->min_len.resize(n_exps);
+  for (int32_t e = 0; e < n_exps; ++e) {
+    // both reverse complements are formed: a character outside ACGTN in either barcode is refused here
+    const int st = make_patterns(exps[e].start_barcode, exps[e].end_barcode, 2, &a->pats[e]);
+    if (st != LVA_OK) return st;
+    a->min_len[e] = exps[e].min_len;
+  }
+  a->max_dist = max_dist < 0 ? -1 : max_dist;
+  a->min_margin = min_margin;
+  return LVA_OK;
+}
+
+struct DemuxDev {
+  BcPatterns* pats;
+  uint32_t *min_len, *best;
+  BcDemuxResult* res;
+  BcResult* all;
+};
+
+size_t demux_bytes(size_t n, size_t k, bool all) {
+  return DevBlock::pad(sizeof(BcPatterns) * k) + DevBlock::pad(4 * k) + DevBlock::pad(16 * n * k) +
+         DevBlock::pad(sizeof(BcDemuxResult) * n) + (all ? DevBlock::pad(sizeof(BcResult) * n * k) : 0);
+}
+
+// search + choice on basecalls that are on the device; copies the results out and waits
+int demux_run(lva_decoder* d, DevBlock* blk, const char* d_bases, const uint32_t* d_trans, const int64_t* d_off,
+              const int32_t* d_nb, int32_t n_reads, const DemuxArgs& a, lva_demux_pos* out, lva_payload_pos* all_out) {
+  static_assert(sizeof(lva_demux_pos) == sizeof(BcDemuxResult), "lva_demux_pos layout");
+  const size_t n = (size_t)n_reads, k = a.pats.size();
+  DemuxDev v;
+  v.pats = blk->take<BcPatterns>(k);
+  v.min_len = blk->take<uint32_t>(k);
+  v.best = blk->take<uint32_t>(4 * n * k);
+  v.res = blk->take<BcDemuxResult>(n);
+  v.all = all_out ? blk->take<BcResult>(n * k) : nullptr;
+  HIP_TRY(hipMemcpyAsync(v.pats, a.pats.data(), sizeof(BcPatterns) * k, hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(v.min_len, a.min_len.data(), 4 * k, hipMemcpyHostToDevice, d->stream));
+  int e = launch_bc_search_multi(d_bases, d_off, d_nb, n_reads, v.pats, (int32_t)k, v.best, d->stream);
+  if (!e) e = launch_bc_demux_finalize(d_trans, d_off, d_nb, n_reads, v.pats, v.min_len, (int32_t)k, a.max_dist, a.min_margin,
+                                       v.best, v.res, v.all, d->stream);
+  if (e) { g_hip_error = hipGetErrorString((hipError_t)e); (void)hipStreamSynchronize(d->stream); return LVA_ERR_HIP; }
+  HIP_TRY(hipMemcpyAsync(out, v.res, sizeof(BcDemuxResult) * n, hipMemcpyDeviceToHost, d->stream));
+  if (all_out) HIP_TRY(hipMemcpyAsync(all_out, v.all, sizeof(BcResult) * n * k, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  return LVA_OK;
+}
+
+// basecall of resident posteriors, then demux_run
+int demux_post(lva_decoder* d, const float* post_dev, const int64_t* row_offsets, int32_t n, const DemuxArgs& a,
+               lva_demux_pos* out, lva_payload_pos* all_out) {
+  if (row_offsets[0] != 0) return LVA_ERR_ARG;
+  for (int32_t i = 0; i < n; ++i)
+    if (row_offsets[i + 1] < row_offsets[i] || row_offsets[i + 1] - row_offsets[i] > kBcMaxBlocks) return LVA_ERR_ARG;
+  const size_t T = (size_t)row_offsets[n];
+  if (T >= ((size_t)1 << 31)) return LVA_ERR_ARG;          // 32-bit block offsets inside the kernels
+  DevBlock blk;
+  blk.cap = DevBlock::pad(8 * ((size_t)n + 1)) + DevBlock::pad(8 * T + 8) + DevBlock::pad(T + n + 1) + DevBlock::pad(T + 1) +
+            DevBlock::pad(4 * T + 4) + DevBlock::pad(4 * (size_t)n) + demux_bytes(n, a.pats.size(), all_out != nullptr);
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&blk.base), blk.cap));
+  int64_t* d_off = blk.take<int64_t>((size_t)n + 1);
+  uint32_t* d_tb = blk.take<uint32_t>(2 * T);          // 8 back-pointer bytes per block
+  uint8_t* d_path = blk.take<uint8_t>(T + n);
+  char* d_bases = blk.take<char>(T);
+  uint32_t* d_trans = blk.take<uint32_t>(T);
+  int32_t* d_nb = blk.take<int32_t>(n);
+  HIP_TRY(hipMemcpyAsync(d_off, row_offsets, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, d->stream));
+  const int e = launch_bc_basecall(post_dev, d_off, n, d_tb, d_path, d_bases, d_trans, d_nb, d->stream);
+  if (e) { g_hip_error = hipGetErrorString((hipError_t)e); (void)hipStreamSynchronize(d->stream); return LVA_ERR_HIP; }
+  const int st = demux_run(d, &blk, d_bases, d_trans, d_off, d_nb, n, a, out, all_out);
+  if (st != LVA_OK) (void)hipStreamSynchronize(d->stream);     // nothing of blk is in use when it is freed
+  return st;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lva_demux_batch_device(lva_decoder* d, const float* post_dev, const int64_t* row_offsets, int32_t n_reads,
+                           const lva_experiment_barcodes* exps, int32_t n_exps, int32_t max_dist, int32_t min_margin,
+                           lva_demux_pos* out, lva_payload_pos* all_out) {
+  if (!d || n_reads < 0 || !row_offsets || (n_reads > 0 && (!post_dev || !out))) return LVA_ERR_ARG;
+  DemuxArgs a;
+  const int st = demux_args(exps, n_exps, max_dist, min_margin, &a);
+  if (st != LVA_OK) return st;
+  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
+  if (n_reads == 0) return LVA_OK;
+  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
+  return demux_post(d, post_dev, row_offsets, n_reads, a, out, all_out);
+}
+
+int lva_demux_batch(lva_decoder* d, const float* post, const int64_t* row_offsets, int32_t n_reads,
+                    const lva_experiment_barcodes* exps, int32_t n_exps, int32_t max_dist, int32_t min_margin,
+                    lva_demux_pos* out, lva_payload_pos* all_out) {
+  if (!d || n_reads < 0 || !row_offsets || (n_reads > 0 && (!post || !out))) return LVA_ERR_ARG;
+  DemuxArgs a;
+  int st = demux_args(exps, n_exps, max_dist, min_margin, &a);
+  if (st != LVA_OK) return st;
+  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
+  if (n_reads == 0) return LVA_OK;
+  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
+  HostPost hp;
+  st = upload_post(d, post, row_offsets, n_reads, &hp);
+  if (st == LVA_OK) st = demux_post(d, hp.dev, row_offsets, n_reads, a, out, all_out);
+  if (st != LVA_OK) (void)hipStreamSynchronize(d->stream);     // the upload may still be in flight
+  return st;
+}
+
+int lva_demux_bases_batch(lva_decoder* d, const char* bases, const uint32_t* trans, const int64_t* base_offsets,
+                          int32_t n_reads, const lva_experiment_barcodes* exps, int32_t n_exps, int32_t max_dist,
+                          int32_t min_margin, lva_demux_pos* out, lva_payload_pos* all_out) {
+  if (!d || n_reads < 0 || !base_offsets || (n_reads > 0 && (!bases || !trans || !out))) return LVA_ERR_ARG;
+  DemuxArgs a;
+  const int st = demux_args(exps, n_exps, max_dist, min_margin, &a);
+  if (st != LVA_OK) return st;
+  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
+  if (n_reads == 0) return LVA_OK;
+  if (base_offsets[0] != 0) return LVA_ERR_ARG;
+  std::vector<int32_t> nb(n_reads);
+  for (int32_t i = 0; i < n_reads; ++i) {
+    if (base_offsets[i + 1] < base_offsets[i] || base_offsets[i + 1] - base_offsets[i] > kBcMaxBlocks) return LVA_ERR_ARG;
+    nb[i] = (int32_t)(base_offsets[i + 1] - base_offsets[i]);
+  }
+  const size_t T = (size_t)base_offsets[n_reads], n = (size_t)n_reads;
+  if (T >= ((size_t)1 << 31)) return LVA_ERR_ARG;
+  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
+  DevBlock blk;
+  blk.cap = DevBlock::pad(8 * (n + 1)) + DevBlock::pad(T + 1) + DevBlock::pad(4 * T + 4) + DevBlock::pad(4 * n) +
+            demux_bytes(n, a.pats.size(), all_out != nullptr);
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&blk.base), blk.cap));
+  int64_t* d_off = blk.take<int64_t>(n + 1);
+  char* d_bases = blk.take<char>(T);
+  uint32_t* d_trans = blk.take<uint32_t>(T);
+  int32_t* d_nb = blk.take<int32_t>(n);
+  int rc = LVA_OK;
+  if (hipMemcpyAsync(d_off, base_offsets, 8 * (n + 1), hipMemcpyHostToDevice, d->stream) != hipSuccess ||
+      (T && hipMemcpyAsync(d_bases, bases, T, hipMemcpyHostToDevice, d->stream) != hipSuccess) ||
+      (T && hipMemcpyAsync(d_trans, trans, 4 * T, hipMemcpyHostToDevice, d->stream) != hipSuccess) ||
+      hipMemcpyAsync(d_nb, nb.data(), 4 * n, hipMemcpyHostToDevice, d->stream) != hipSuccess) {
+    g_hip_error = "hipMemcpyAsync (demultiplexing inputs)";
+    rc = LVA_ERR_HIP;
+  }
+  if (rc == LVA_OK) rc = demux_run(d, &blk, d_bases, d_trans, d_off, d_nb, n_reads, a, out, all_out);
+  if (rc != LVA_OK) (void)hipStreamSynchronize(d->stream);     // nb and blk are released on return
+  return rc;
+}
+
+}  // extern "C"
+
 /* ---------------------------------------------------------------------------------------------
  * the consumers of a decoded list (csrc/ls_kernels.hip).  Like the RS entry
  * points they take a device ordinal, work on a stream of their own and leave every decoder's profile alone.

@@ -312,6 +312,69 @@ class Decoder:
                                                             end_barcode.encode(), self.mem_conv + self.msg_len + 1, res))
         return self._payload_out(res, n)
 
+    # --- DESIGN.md row N3': demultiplexing a pooled run ------------------------------------------
+    @staticmethod
+    def _demux_args(experiments, max_dist, min_margin):
+        from .helper import experiment_barcodes
+        exps = [experiment_barcodes(e) for e in experiments]
+        arr = (_lib.ExperimentBarcodes * max(len(exps), 1))()
+        for a, (sb, eb, min_len) in zip(arr, exps):
+            a.start_barcode, a.end_barcode, a.min_len = sb.encode(), eb.encode(), min_len
+        return arr, len(exps), -1 if max_dist is None or max_dist < 0 else int(max_dist), int(min_margin)
+
+    def _demux_out(self, res, table, n, k, all):
+        inf, big = float("inf"), 0x7FFFFFFF
+        out = []
+        for r, d in zip(res[:n], self._payload_out([r.pos for r in res[:n]], n)):
+            d.update(experiment=r.experiment, reason=r.reason, runner_up=r.runner_up,
+                     runner_up_dist=inf if r.runner_up_dist == big else r.runner_up_dist)
+            out.append(d)
+        if not all:
+            return out
+        return out, [self._payload_out(table[i * k:(i + 1) * k], k) for i in range(n)]
+
+    def demux(self, posts, experiments, max_dist=None, min_margin=0, all=False):
+        """Which experiment of a pooled run each read belongs to: one basecall per read, one search over every experiment's
+        barcodes, one decision (helper.demux_barcodes is the host counterpart).  experiments: (start_barcode, end_barcode,
+        min_len) tuples or dicts (helper.experiment_barcodes), 1..64 of them.
+        -> [dict(locate_payload's fields of the winner, experiment, reason, runner_up, runner_up_dist)];
+        all=True: -> (that, [[locate_payload dict per experiment] per read])."""
+        n = len(posts)
+        flat, off = self._pack(posts)
+        arr, k, md, mm = self._demux_args(experiments, max_dist, min_margin)
+        res = (_lib.DemuxPos * max(n, 1))()
+        table = (_lib.PayloadPos * max(n * k, 1))() if all else None
+        self._check(self._L.lva_demux_batch(self._h, flat.ctypes.data, off.ctypes.data, n, arr, k, md, mm, res, table))
+        return self._demux_out(res, table, n, k, all)
+
+    def demux_resident(self, dev_ptr, off, experiments, max_dist=None, min_margin=0, all=False):
+        """demux() on a resident posterior buffer (upload(), posteriors_resident())"""
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        n = len(off) - 1
+        arr, k, md, mm = self._demux_args(experiments, max_dist, min_margin)
+        res = (_lib.DemuxPos * max(n, 1))()
+        table = (_lib.PayloadPos * max(n * k, 1))() if all else None
+        self._check(self._L.lva_demux_batch_device(self._h, dev_ptr, off.ctypes.data, n, arr, k, md, mm, res, table))
+        return self._demux_out(res, table, n, k, all)
+
+    def demux_bases(self, basecalls, trans_lists, experiments, max_dist=None, min_margin=0, all=False):
+        """demux() on given (basecall, trans list) pairs, as find_barcode takes them, in both orientations"""
+        n = len(basecalls)
+        off = np.zeros(n + 1, np.int64)
+        off[1:] = np.cumsum([len(b) for b in basecalls])
+        for b, t in zip(basecalls, trans_lists):
+            if len(t) < len(b):
+                raise ValueError("trans list shorter than the basecall")
+        bases = np.frombuffer("".join(basecalls).encode("ascii") or b"\0", dtype=np.uint8).copy()
+        trans = np.concatenate([np.asarray(t, dtype=np.uint32)[:len(b)] for b, t in zip(basecalls, trans_lists)]
+                               + [np.zeros(1, np.uint32)])
+        arr, k, md, mm = self._demux_args(experiments, max_dist, min_margin)
+        res = (_lib.DemuxPos * max(n, 1))()
+        table = (_lib.PayloadPos * max(n * k, 1))() if all else None
+        self._check(self._L.lva_demux_bases_batch(self._h, bases.ctypes.data, trans.ctypes.data, off.ctypes.data, n,
+                                                  arr, k, md, mm, res, table))
+        return self._demux_out(res, table, n, k, all)
+
     def decode_with_barcodes(self, posts, start_barcode, end_barcode):
         """The real-data chain of generate_decoded_lists.py:68-89 on the device: posteriors are uploaded once,
         payload windows located, then decoded in place.  -> [(locate dict, decode result or None)]"""

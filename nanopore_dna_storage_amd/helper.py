@@ -73,6 +73,73 @@ def find_barcode_pos_in_post(trans_filename, fastq_filename, start_barcode, end_
     return (r["start_pos"], r["end_pos"], r["dist_start"], r["dist_end"])
 
 
+DEMUX_REASONS = {0: "assigned", 1: "no barcode pair located", 2: "barcode distance above max_dist",
+                 3: "runner-up within min_margin", 4: "payload window shorter than the code"}
+
+
+def experiment_barcodes(exp):
+    """One experiment of a pooled run -> (start_barcode, end_barcode, min_len).  `exp`: a (start, end[, min_len]) tuple, or a
+    dict with start_barcode, end_barcode and either min_len or the code (mem_conv, msg_len: min_len = mem_conv + msg_len + 1,
+    generate_decoded_lists.py:76); min_len defaults to 0."""
+    if isinstance(exp, dict):
+        if "min_len" in exp:
+            min_len = exp["min_len"]
+        elif "mem_conv" in exp and "msg_len" in exp:
+            min_len = exp["mem_conv"] + exp["msg_len"] + 1
+        else:
+            min_len = 0
+        return exp["start_barcode"], exp["end_barcode"], int(min_len)
+    exp = tuple(exp)
+    return exp[0], exp[1], int(exp[2]) if len(exp) > 2 else 0
+
+
+def demux_barcodes(basecall, trans, experiments, max_dist=None, min_margin=0, all=False):
+    """Which experiment of a pooled run a read belongs to (the table of encode_experiments.py:3-33; the reference sorts its
+    reads with util/align_compute_stats.sh + util/generate_read_id_file.py): generate_decoded_lists.py:68-79 for every
+    experiment's barcode pair on ONE basecall, then the choice.  Host counterpart and yardstick of Decoder.demux*.
+    A candidate is located when start_pos != -1, its total is dist_start + dist_end.  The smallest total wins (the lowest
+    experiment on a draw); the runner-up is the best located candidate of the other experiments.  reason: 1 nothing located,
+    2 total > max_dist, 3 runner_up_dist - total < min_margin, 4 window shorter than the winner's min_len, else 0.
+    -> dict(ok, start_pos, end_pos, rc, dist_start, dist_end, experiment, reason, runner_up, runner_up_dist);
+    all=True: -> (that, [candidate dict per experiment])."""
+    inf = float("inf")
+    exps = [experiment_barcodes(e) for e in experiments]
+    if not 1 <= len(exps) <= 64:
+        raise ValueError("1..64 experiments")
+    if min_margin < 0:
+        raise ValueError("min_margin >= 0")
+    table = []
+    for sb, eb, min_len in exps:
+        if not sb or not eb or len(sb) > 64 or len(eb) > 64:
+            raise ValueError("barcodes: 1..64 characters")
+        fwd = find_barcode_pos(basecall, trans, sb, eb)
+        rev = find_barcode_pos(basecall, trans, reverse_complement(eb), reverse_complement(sb))
+        rc = fwd[2] + fwd[3] > rev[2] + rev[3]                            # generate_decoded_lists.py:71
+        sp, ep, ds, de = rev if rc else fwd
+        table.append(dict(ok=not (sp == -1 or ep - sp + 1 < min_len), start_pos=sp, end_pos=ep, rc=bool(rc),
+                          dist_start=ds, dist_end=de))
+    located = [e for e, c in enumerate(table) if c["start_pos"] != -1]
+    if not located:
+        res = dict(ok=False, start_pos=-1, end_pos=-1, rc=False, dist_start=inf, dist_end=inf, experiment=-1, reason=1,
+                   runner_up=-1, runner_up_dist=inf)
+        return (res, table) if all else res
+    total = lambda e: table[e]["dist_start"] + table[e]["dist_end"]
+    win = min(located, key=lambda e: (total(e), e))
+    others = [e for e in located if e != win]
+    ru = min(others, key=lambda e: (total(e), e)) if others else -1
+    ru_dist = total(ru) if ru >= 0 else inf
+    if max_dist is not None and max_dist >= 0 and total(win) > max_dist:
+        reason = 2
+    elif ru_dist - total(win) < min_margin:
+        reason = 3
+    elif not table[win]["ok"]:
+        reason = 4
+    else:
+        reason = 0
+    res = dict(table[win], ok=reason == 0, experiment=win, reason=reason, runner_up=ru, runner_up_dist=ru_dist)
+    return (res, table) if all else res
+
+
 def truncate_post(post, start_pos, end_pos):
     """rows [start_pos, end_pos] (inclusive) of a [nblk, 40] posterior matrix"""
     post = np.asarray(post, dtype=np.float32).reshape(-1, 40)

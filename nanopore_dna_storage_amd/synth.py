@@ -190,3 +190,28 @@ def make_reads(mem_conv, rate, msg_len, n, seed0=0, rc_mode="none", margin=6.0, 
         rc = rc_mode == "all" or (rc_mode == "odd" and (i & 1))
         reads.append(make_read(mem_conv, rate, msg_len, seed0 + i, rc=rc, margin=margin, **kw))
     return reads
+
+
+def random_barcode(rng, length=25):
+    return "".join(BASES[int(x)] for x in rng.integers(0, 4, size=length))
+
+
+def make_pooled_reads(experiments, n, seed0=0, assign=None, scores=False, rc_mode="seed", **kw):
+    """Reads of a pooled run: read i is a make_barcoded_read (scores=True: make_barcoded_read_scores) of seed seed0 + i with
+    the barcodes and the code of ITS experiment.  experiments: dicts with start_barcode, end_barcode, mem_conv, rate_conv,
+    msg_len (what pooled.read_experiments returns).  The experiment (and, rc_mode="seed", the strand) of a read is drawn
+    from its seed unless `assign` (one experiment index per read) is given; rc_mode: 'seed', 'none', 'all', 'odd'.
+    -> (reads, true experiment index per read)"""
+    make = make_barcoded_read_scores if scores else make_barcoded_read
+    reads, truth = [], []
+    for i in range(n):
+        pick = np.random.default_rng([seed0 + i, 0x706F6F6C])               # not the stream the read itself is drawn from
+        e = int(pick.integers(len(experiments)))
+        rc_seed = bool(pick.integers(2))
+        if assign is not None:
+            e = int(assign[i])
+        rc = {"seed": rc_seed, "none": False, "all": True, "odd": bool(i & 1)}[rc_mode]
+        x = experiments[e]
+        reads.append(make(x["mem_conv"], x["rate_conv"], x["msg_len"], seed0 + i, x["start_barcode"], x["end_barcode"], rc=rc, **kw))
+        truth.append(e)
+    return reads, truth

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Register / LDS / scratch usage of every kernel in lva_kernels.hip (from the gfx950 assembly metadata).
+# SRC=bc_kernels.hip scripts/kernel_regs.sh: the same for another file of csrc/.
 cd "$(dirname "$0")/../nanopore_dna_storage_amd/csrc"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math --cuda-device-only $1 -S -o /tmp/lva_k.s lva_kernels.hip || exit 1
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math --cuda-device-only $1 -S -o /tmp/lva_k.s "${SRC:-lva_kernels.hip}" || exit 1
 python3 - <<'PY'
 import re
 t = open('/tmp/lva_k.s').read()
