@@ -1,4 +1,5 @@
-// lva_api.cpp -- C ABI (include/lva_decoder.h) and the host driver of the trellis kernels.
+// lva_api.cpp -- C ABI (include/lva_decoder.h) and the host driver of the trellis kernels: the decoder, its schedule,
+// the decode stream, lva_decode_* and lva_device_*.  The stages beside the decoder are in lva_stages.cpp.
 //
 // Scheduling: reads are independent.  The decoder keeps S read slots resident in
 // HBM; one trellis-step launch advances every active slot by one time step of its own read,
@@ -6,8 +7,6 @@
 // re-initialised for the next read while the others continue ("continuous batching" of the
 // reference's sequential time loop :667).  Everything is enqueued on one HIP stream without
 // host synchronisation until the results are copied back.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -16,80 +15,15 @@
 #include <deque>
 #include <limits>
 #include <numeric>
-#include <string>
-#include <vector>
 
-#include "../../include/lva_decoder.h"
-#include "lva_code.h"
-#include "lva_device.h"
+#include "lva_host.h"
 #include "lva_kernels.h"
-#include "bc_kernels.h"
-#include "tp_kernels.h"
-#include "ls_kernels.h"
 
 using namespace lva;
 
-namespace {
+static thread_local std::string g_hip_error;
 
-thread_local std::string g_hip_error;
-
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e__ = (expr);                                                                   \
-    if (e__ != hipSuccess) {                                                                   \
-      g_hip_error = std::string(#expr) + ": " + hipGetErrorString(e__);                        \
-      return LVA_ERR_HIP;                                                                      \
-    }                                                                                          \
-  } while (0)
-
-}  // namespace
-
-struct lva_stream;
-
-struct lva_decoder {
-  lva_config cfg{};
-  std::string sync_marker;
-  Code code[2];                // forward, reverse complement
-  uint32_t max_dev = 0;
-  Geometry g{};
-  int slots = 0;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_total0 = nullptr, ev_total1 = nullptr, ev_step0 = nullptr, ev_step1 = nullptr, ev_h2d = nullptr;
-  DevCode* d_codes = nullptr;
-  uint16_t* d_predtab = nullptr;
-  uint32_t* d_trellis = nullptr;
-  uint32_t* d_results = nullptr;
-  size_t results_cap = 0;      // reads
-  SlotDesc* d_slots = nullptr; // [slots]
-  SlotStep* d_steps = nullptr; // [slots] this launch's time step of every slot (lva_prepare_step)
-  uint32_t* d_band = nullptr;  // band tables of the batch in flight: lo | hi << 16 per (read, time step)
-  size_t band_cap = 0;         // words
-  WorkHdr* d_work = nullptr;   // header followed by the item array
-  uint32_t work_cap = 1u << 20;
-  int kernel = 1;              // 1 = exact, 2 = fast + exact fix-up
-  uint32_t launch_no = 0;      // trellis-step launches since creation (the slots' clock)
-  uint32_t full_lo = 1, full_hi = 0;   // positions at which every 64-source tile has a valid target (StepArgs::full_lo/hi)
-  int launch_events = 0;       // lva_decoder_set_launch_events
-  std::vector<hipEvent_t> ev_pool;
-  lva_profile prof{};
-  lva_stream* open_stream = nullptr;   // lva_stream_open .. lva_stream_close: the batch entry points refuse meanwhile
-  float* d_tp_fwd = nullptr;   // lva_transpost_*: forward vectors, 8 floats per block; grows, never shrinks
-  size_t tp_fwd_cap = 0;       // blocks
-  int64_t* d_tp_off = nullptr; // lva_transpost_*: row offsets of the batch
-  size_t tp_off_cap = 0;       // entries
-};
-
-namespace {
-// every error exit of a call that has enqueued asynchronous work drains the stream first: pending
-// device->host copies target buffers that die with the call's frame
-struct StreamDrain {
-  hipStream_t s;
-  bool armed = true;
-  explicit StreamDrain(hipStream_t st) : s(st) {}
-  ~StreamDrain() { if (armed && s) (void)hipStreamSynchronize(s); }
-};
-}  // namespace
+void lva::set_hip_error(const std::string& text) { g_hip_error = text; }
 
 extern "C" {
 
@@ -533,14 +467,12 @@ struct Schedule {
   int flush_inits() {
     const int e = launch_init_slots(d->g, d->d_codes, d->d_trellis, ib, d->d_slots, d->stream);
     ib.n = 0;
-    if (e) { g_hip_error = hipGetErrorString((hipError_t)e); return LVA_ERR_HIP; }
-    return LVA_OK;
+    return launch_status(e);
   }
   int flush_gathers() {
     const int e = launch_gather_finals(d->g, d->d_codes, d->d_trellis, gb, results, d->stream);
     gb.n = 0;
-    if (e) { g_hip_error = hipGetErrorString((hipError_t)e); return LVA_ERR_HIP; }
-    return LVA_OK;
+    return launch_status(e);
   }
   // a read enters idle slot s: its descriptor and initial scores (:657-663) go in stream order, a batch of slots per launch
   // (behind the gathers of the reads that left them: retire runs before the next fill)
@@ -574,7 +506,7 @@ struct Schedule {
     a.full_lo = d->full_lo; a.full_hi = d->full_hi; a.pad = 0;
     {
       const int e = launch_prepare_step(a, d->d_codes, d->d_steps, d->stream);
-      if (e) { g_hip_error = hipGetErrorString((hipError_t)e); return LVA_ERR_HIP; }
+      if (e) return launch_status(e);
     }
     hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
     if (launch_events) {
@@ -591,7 +523,7 @@ struct Schedule {
                         ? launch_step_fast(a, d->g, d->d_codes, d->d_trellis, d->d_work, reinterpret_cast<uint32_t*>(d->d_work + 1), d->stream, e1)
                         : d->kernel == 3 ? launch_step_wave(a, d->g, d->d_codes, d->d_trellis, d->stream)
                                          : launch_step_exact(a, d->g, d->d_codes, d->d_trellis, d->stream);
-      if (e) { g_hip_error = hipGetErrorString((hipError_t)e); return LVA_ERR_HIP; }
+      if (e) return launch_status(e);
     }
     if (e2) {
       if (d->kernel != 2 && d->kernel != 4) HIP_TRY(hipEventRecord(e1, d->stream));
@@ -1054,22 +986,21 @@ int lva_decode_batch(lva_decoder* d, const float* post, const int64_t* row_offse
   if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
   const int64_t blocks = n_reads > 0 ? row_offsets[n_reads] : 0;
   if (blocks < 0) return LVA_ERR_ARG;
-  float* dev = nullptr;
+  HostPost hp;                               // freed on every exit below, each behind a drained stream
   const size_t bytes = (size_t)std::max<int64_t>(blocks, 1) * 40 * sizeof(float);
-  HIP_TRY(hipMalloc(&dev, bytes));
+  HIP_TRY(hipMalloc(&hp.dev, bytes));
   hipError_t e = hipEventRecord(d->ev_total0, d->stream);
   if (e == hipSuccess && blocks > 0)
-    e = hipMemcpyAsync(dev, post, (size_t)blocks * 40 * sizeof(float), hipMemcpyHostToDevice, d->stream);
+    e = hipMemcpyAsync(hp.dev, post, (size_t)blocks * 40 * sizeof(float), hipMemcpyHostToDevice, d->stream);
   if (e == hipSuccess) e = hipEventRecord(d->ev_h2d, d->stream);
-  if (e != hipSuccess) { g_hip_error = hipGetErrorString(e); (void)hipStreamSynchronize(d->stream); (void)hipFree(dev); return LVA_ERR_HIP; }
+  if (e != hipSuccess) { g_hip_error = hipGetErrorString(e); (void)hipStreamSynchronize(d->stream); return LVA_ERR_HIP; }
   std::vector<int64_t> len((size_t)n_reads);
   for (int32_t i = 0; i < n_reads; ++i) len[i] = row_offsets[i + 1] - row_offsets[i];
-  const int st = decode_impl(d, dev, row_offsets, len.data(), n_reads, rc_flags, out_msgs, out_scores, out_counts, true);
+  const int st = decode_impl(d, hp.dev, row_offsets, len.data(), n_reads, rc_flags, out_msgs, out_scores, out_counts, true);
   (void)hipStreamSynchronize(d->stream);
   float ms = 0;
   d->prof.h2d_ms = (st == LVA_OK && hipEventElapsedTime(&ms, d->ev_total0, d->ev_h2d) == hipSuccess) ? ms : 0.0;
   d->prof.h2d_bytes = (uint64_t)blocks * 40 * sizeof(float);
-  (void)hipFree(dev);
   return st;
 }
 
@@ -1107,589 +1038,6 @@ int lva_device_synchronize(lva_decoder* d) {
   if (!d) return LVA_ERR_ARG;
   HIP_TRY(hipSetDevice(d->device));
   HIP_TRY(hipStreamSynchronize(d->stream));
-  return LVA_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------
-// basecall of the posterior matrix and barcode localisation.
-// ---------------------------------------------------------------------------------------------
-namespace {
-
-// bc_search packs (edit distance << 20 | window index) into one word for its minimum reduction
-// (bc_kernels.hip): a read may have at most 2^20 blocks / called bases.  Real reads have a few thousand.
-constexpr int64_t kBcMaxBlocks = (int64_t)1 << 20;
-
-struct DevBlock {              // one device allocation carved into 256-byte aligned pieces
-  char* base = nullptr;
-  size_t used = 0, cap = 0;
-  ~DevBlock() { if (base) (void)hipFree(base); }
-  static size_t pad(size_t b) { return (b + 255) & ~(size_t)255; }
-  template <typename T> T* take(size_t count) {
-    T* p = reinterpret_cast<T*>(base + used);
-    used += pad(std::max<size_t>(count, 1) * sizeof(T));
-    return p;
-  }
-};
-
-bool rc_pattern(const char* src, int len, char* dst) {        // helper.reverse_complement (helper.py:227-229)
-  for (int i = 0; i < len; ++i) {
-    char c;
-    switch (src[len - 1 - i]) {
-      case 'A': c = 'T'; break;
-      case 'C': c = 'G'; break;
-      case 'G': c = 'C'; break;
-      case 'T': c = 'A'; break;
-      case 'N': c = 'N'; break;
-      default: return false;
-    }
-    dst[i] = c;
-  }
-  return true;
-}
-
-int make_patterns(const char* start_bc, const char* end_bc, int n_orient, BcPatterns* p) {
-  if (!start_bc || !end_bc) return LVA_ERR_ARG;
-  const size_t ls = std::strlen(start_bc), le = std::strlen(end_bc);
-  if (ls == 0 || le == 0 || ls > (size_t)kMaxBarcode || le > (size_t)kMaxBarcode) return LVA_ERR_ARG;
-  std::memset(p, 0, sizeof *p);
-  p->len[0] = (uint8_t)ls; p->len[1] = (uint8_t)le;
-  std::memcpy(p->pat[0], start_bc, ls);
-  std::memcpy(p->pat[1], end_bc, le);
-  if (n_orient == 2) {         // generate_decoded_lists.py:33-34: START_BARCODE_RC = rc(END), END_BARCODE_RC = rc(START)
-    p->len[2] = (uint8_t)le; p->len[3] = (uint8_t)ls;
-    if (!rc_pattern(end_bc, (int)le, p->pat[2]) || !rc_pattern(start_bc, (int)ls, p->pat[3])) return LVA_ERR_ARG;
-  }
-  return LVA_OK;
-}
-
-// basecall (and, when n_orient > 0, barcode localisation) of n reads whose posteriors are resident
-int bc_run(lva_decoder* d, const float* post_dev, const int64_t* row_offsets, int32_t n, const BcPatterns* pat,
-           int n_orient, uint32_t min_len, char* bases_out, uint32_t* trans_out, int32_t* nbases_out,
-           lva_payload_pos* pos_out) {
-  static_assert(sizeof(lva_payload_pos) == sizeof(BcResult), "lva_payload_pos layout");
-  if (n == 0) return LVA_OK;
-  for (int32_t i = 0; i < n; ++i)
-    if (row_offsets[i + 1] < row_offsets[i] || row_offsets[i + 1] - row_offsets[i] > kBcMaxBlocks) return LVA_ERR_ARG;
-  const size_t T = (size_t)(row_offsets[n] - row_offsets[0]);
-  if (T >= ((size_t)1 << 31)) return LVA_ERR_ARG;          // 32-bit block offsets inside the kernels
-  if (row_offsets[0] != 0) return LVA_ERR_ARG;
-  DevBlock blk;
-  blk.cap = DevBlock::pad(8 * ((size_t)n + 1)) + DevBlock::pad(8 * T + 8) + DevBlock::pad(T + n + 1) + DevBlock::pad(T + 1) +
-            DevBlock::pad(4 * T + 4) + DevBlock::pad(4 * (size_t)n) + DevBlock::pad(16 * (size_t)n) + DevBlock::pad(24 * (size_t)n);
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&blk.base), blk.cap));
-  int64_t* d_off = blk.take<int64_t>((size_t)n + 1);
-  uint32_t* d_tb = blk.take<uint32_t>(2 * T);          // 8 back-pointer bytes per block
-  uint8_t* d_path = blk.take<uint8_t>(T + n);
-  char* d_bases = blk.take<char>(T);
-  uint32_t* d_trans = blk.take<uint32_t>(T);
-  int32_t* d_nb = blk.take<int32_t>(n);
-  uint32_t* d_best = blk.take<uint32_t>(4 * (size_t)n);
-  BcResult* d_res = blk.take<BcResult>(n);
-  HIP_TRY(hipMemcpyAsync(d_off, row_offsets, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, d->stream));
-  int e = launch_bc_basecall(post_dev, d_off, n, d_tb, d_path, d_bases, d_trans, d_nb, d->stream);
-  if (!e && n_orient > 0) e = launch_bc_search(d_bases, d_off, d_nb, n, *pat, n_orient, d_best, d->stream);
-  if (!e && n_orient > 0) e = launch_bc_finalize(d_trans, d_off, d_nb, n, *pat, n_orient, min_len, d_best, d_res, d->stream);
-  if (e) { g_hip_error = hipGetErrorString((hipError_t)e); return LVA_ERR_HIP; }
-  if (bases_out && T) HIP_TRY(hipMemcpyAsync(bases_out, d_bases, T, hipMemcpyDeviceToHost, d->stream));
-  if (trans_out && T) HIP_TRY(hipMemcpyAsync(trans_out, d_trans, 4 * T, hipMemcpyDeviceToHost, d->stream));
-  if (nbases_out) HIP_TRY(hipMemcpyAsync(nbases_out, d_nb, 4 * (size_t)n, hipMemcpyDeviceToHost, d->stream));
-  if (pos_out && n_orient > 0) HIP_TRY(hipMemcpyAsync(pos_out, d_res, sizeof(BcResult) * (size_t)n, hipMemcpyDeviceToHost, d->stream));
-  HIP_TRY(hipStreamSynchronize(d->stream));
-  return LVA_OK;
-}
-
-// host posteriors -> device copy for the duration of the call
-struct HostPost {
-  float* dev = nullptr;
-  ~HostPost() { if (dev) (void)hipFree(dev); }
-};
-
-int upload_post(lva_decoder* d, const float* post, const int64_t* row_offsets, int32_t n, HostPost* hp) {
-  const int64_t blocks = n > 0 ? row_offsets[n] : 0;
-  if (blocks < 0) return LVA_ERR_ARG;
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&hp->dev), (size_t)std::max<int64_t>(blocks, 1) * 160));
-  if (blocks > 0) HIP_TRY(hipMemcpyAsync(hp->dev, post, (size_t)blocks * 160, hipMemcpyHostToDevice, d->stream));
-  return LVA_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int lva_basecall_batch_device(lva_decoder* d, const float* post_dev, const int64_t* row_offsets, int32_t n_reads,
-                              char* bases_out, uint32_t* trans_out, int32_t* nbases_out) {
-  if (!d || n_reads < 0 || !row_offsets || (n_reads > 0 && (!post_dev || !nbases_out))) return LVA_ERR_ARG;
-  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
-  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
-  return bc_run(d, post_dev, row_offsets, n_reads, nullptr, 0, 0, bases_out, trans_out, nbases_out, nullptr);
-}
-
-int lva_basecall_batch(lva_decoder* d, const float* post, const int64_t* row_offsets, int32_t n_reads, char* bases_out,
-                       uint32_t* trans_out, int32_t* nbases_out) {
-  if (!d || n_reads < 0 || !row_offsets || (n_reads > 0 && (!post || !nbases_out))) return LVA_ERR_ARG;
-  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
-  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
-  HostPost hp;
-  const int st = upload_post(d, post, row_offsets, n_reads, &hp);
-  if (st != LVA_OK) return st;
-  return bc_run(d, hp.dev, row_offsets, n_reads, nullptr, 0, 0, bases_out, trans_out, nbases_out, nullptr);
-}
-
-int lva_locate_payload_batch_device(lva_decoder* d, const float* post_dev, const int64_t* row_offsets, int32_t n_reads,
-                                    const char* start_barcode, const char* end_barcode, uint32_t min_len,
-                                    lva_payload_pos* out) {
-  if (!d || n_reads < 0 || !row_offsets || (n_reads > 0 && (!post_dev || !out))) return LVA_ERR_ARG;
-  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
-  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
-  BcPatterns pat;
-  const int st = make_patterns(start_barcode, end_barcode, 2, &pat);
-  if (st != LVA_OK) return st;
-  return bc_run(d, post_dev, row_offsets, n_reads, &pat, 2, min_len, nullptr, nullptr, nullptr, out);
-}
-
-int lva_locate_payload_batch(lva_decoder* d, const float* post, const int64_t* row_offsets, int32_t n_reads,
-                             const char* start_barcode, const char* end_barcode, uint32_t min_len, lva_payload_pos* out) {
-  if (!d || n_reads < 0 || !row_offsets || (n_reads > 0 && (!post || !out))) return LVA_ERR_ARG;
-  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
-  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
-  BcPatterns pat;
-  int st = make_patterns(start_barcode, end_barcode, 2, &pat);
-  if (st != LVA_OK) return st;
-  HostPost hp;
-  st = upload_post(d, post, row_offsets, n_reads, &hp);
-  if (st != LVA_OK) return st;
-  return bc_run(d, hp.dev, row_offsets, n_reads, &pat, 2, min_len, nullptr, nullptr, nullptr, out);
-}
-
-// ---------------------------------------------------------------------------------------------
-// transition posteriors from a network's transition scores.
-// ---------------------------------------------------------------------------------------------
-}  // extern "C"
-
-namespace {
-
-// the limits of the basecall entry points, from the offsets alone: nothing is allocated for a batch that breaks them
-int tp_check(const int64_t* row_offsets, int32_t n, size_t* total) {
-  *total = 0;
-  if (n == 0) return LVA_OK;
-  if (row_offsets[0] != 0) return LVA_ERR_ARG;
-  for (int32_t i = 0; i < n; ++i)
-    if (row_offsets[i + 1] < row_offsets[i] || row_offsets[i + 1] - row_offsets[i] > kBcMaxBlocks) return LVA_ERR_ARG;
-  if (row_offsets[n] >= ((int64_t)1 << 31)) return LVA_ERR_ARG;
-  *total = (size_t)row_offsets[n];
-  return LVA_OK;
-}
-
-// forward and backward kernel over n reads resident on the device; post_dev may be scores_dev.  Enqueues only.
-int tp_run(lva_decoder* d, const float* scores_dev, const int64_t* row_offsets, int32_t n, size_t T, float* post_dev) {
-  if (((uintptr_t)scores_dev | (uintptr_t)post_dev) & 15u) return LVA_ERR_ARG;     // 16-byte row requests
-  if (T > d->tp_fwd_cap) {
-    HIP_TRY(hipStreamSynchronize(d->stream));
-    if (d->d_tp_fwd) (void)hipFree(d->d_tp_fwd);
-    d->d_tp_fwd = nullptr; d->tp_fwd_cap = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&d->d_tp_fwd), T * 8 * sizeof(float)) != hipSuccess) return LVA_ERR_NOMEM;
-    d->tp_fwd_cap = T;
-  }
-  if ((size_t)n + 1 > d->tp_off_cap) {
-    HIP_TRY(hipStreamSynchronize(d->stream));
-    if (d->d_tp_off) (void)hipFree(d->d_tp_off);
-    d->d_tp_off = nullptr; d->tp_off_cap = 0;
-    const size_t cap = std::max<size_t>((size_t)n + 1, 1024);
-    if (hipMalloc(reinterpret_cast<void**>(&d->d_tp_off), cap * sizeof(int64_t)) != hipSuccess) return LVA_ERR_NOMEM;
-    d->tp_off_cap = cap;
-  }
-  HIP_TRY(hipMemcpyAsync(d->d_tp_off, row_offsets, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(hipEventRecord(d->ev_total0, d->stream));
-  int e = launch_tp_forward(scores_dev, d->d_tp_off, n, d->d_tp_fwd, d->stream);
-  if (!e) e = launch_tp_backward(scores_dev, d->d_tp_off, n, d->d_tp_fwd, post_dev, d->stream);
-  if (e) { g_hip_error = hipGetErrorString((hipError_t)e); return LVA_ERR_HIP; }
-  HIP_TRY(hipEventRecord(d->ev_total1, d->stream));
-  return LVA_OK;
-}
-
-// the profile after a posterior call: the two kernels' HIP-event time and the blocks they covered
-int tp_profile(lva_decoder* d, size_t T, bool timed) {
-  const int32_t slots = d->prof.slots, kernel = d->prof.kernel;
-  d->prof = lva_profile{};
-  d->prof.slots = slots; d->prof.kernel = kernel;
-  d->prof.read_steps = T;
-  float ms = 0;
-  if (timed) HIP_TRY(hipEventElapsedTime(&ms, d->ev_total0, d->ev_total1));
-  d->prof.total_ms = ms;
-  return LVA_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int lva_transpost_batch_device(lva_decoder* d, const float* scores_dev, const int64_t* row_offsets, int32_t n_reads,
-                               float* post_dev) {
-  if (!d || n_reads < 0 || !row_offsets) return LVA_ERR_ARG;
-  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the decoder's HIP stream and the profile
-  size_t T = 0;
-  const int st = tp_check(row_offsets, n_reads, &T);
-  if (st != LVA_OK) return st;
-  if (T > 0 && (!scores_dev || !post_dev)) return LVA_ERR_ARG;
-  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
-  if (T == 0) return tp_profile(d, 0, false);
-  StreamDrain drain(d->stream);              // the offsets are copied from the caller's memory
-  const int rs = tp_run(d, scores_dev, row_offsets, n_reads, T, post_dev);
-  if (rs != LVA_OK) return rs;
-  drain.armed = false;
-  HIP_TRY(hipStreamSynchronize(d->stream));
-  return tp_profile(d, T, true);
-}
-
-int lva_transpost_batch(lva_decoder* d, const float* scores, const int64_t* row_offsets, int32_t n_reads, float* post_out) {
-  if (!d || n_reads < 0 || !row_offsets) return LVA_ERR_ARG;
-  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the decoder's HIP stream and the profile
-  size_t T = 0;
-  int st = tp_check(row_offsets, n_reads, &T);
-  if (st != LVA_OK) return st;
-  if (T > 0 && (!scores || !post_out)) return LVA_ERR_ARG;
-  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
-  if (T == 0) return tp_profile(d, 0, false);
-  HostPost hp;
-  StreamDrain drain(d->stream);
-  st = upload_post(d, scores, row_offsets, n_reads, &hp);
-  if (st != LVA_OK) return st;
-  st = tp_run(d, hp.dev, row_offsets, n_reads, T, hp.dev);
-  if (st != LVA_OK) return st;
-  HIP_TRY(hipMemcpyAsync(post_out, hp.dev, T * 160, hipMemcpyDeviceToHost, d->stream));
-  drain.armed = false;
-  HIP_TRY(hipStreamSynchronize(d->stream));
-  return tp_profile(d, T, true);
-}
-
-int lva_find_barcode_batch(lva_decoder* d, const char* bases, const uint32_t* trans, const int64_t* base_offsets,
-                           int32_t n_reads, const char* start_barcode, const char* end_barcode, lva_payload_pos* out) {
-  if (!d || n_reads < 0 || !base_offsets || (n_reads > 0 && (!bases || !trans || !out))) return LVA_ERR_ARG;
-  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
-  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
-  if (n_reads == 0) return LVA_OK;
-  BcPatterns pat;
-  const int st = make_patterns(start_barcode, end_barcode, 1, &pat);
-  if (st != LVA_OK) return st;
-  if (base_offsets[0] != 0) return LVA_ERR_ARG;
-  std::vector<int32_t> nb(n_reads);
-  for (int32_t i = 0; i < n_reads; ++i) {
-    if (base_offsets[i + 1] < base_offsets[i] || base_offsets[i + 1] - base_offsets[i] > kBcMaxBlocks) return LVA_ERR_ARG;
-    nb[i] = (int32_t)(base_offsets[i + 1] - base_offsets[i]);
-  }
-  const size_t T = (size_t)base_offsets[n_reads], n = (size_t)n_reads;
-  DevBlock blk;
-  blk.cap = DevBlock::pad(8 * (n + 1)) + DevBlock::pad(T + 1) + DevBlock::pad(4 * T + 4) + DevBlock::pad(4 * n) +
-            DevBlock::pad(16 * n) + DevBlock::pad(24 * n);
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&blk.base), blk.cap));
-  int64_t* d_off = blk.take<int64_t>(n + 1);
-  char* d_bases = blk.take<char>(T);
-  uint32_t* d_trans = blk.take<uint32_t>(T);
-  int32_t* d_nb = blk.take<int32_t>(n);
-  uint32_t* d_best = blk.take<uint32_t>(4 * n);
-  BcResult* d_res = blk.take<BcResult>(n);
-  HIP_TRY(hipMemcpyAsync(d_off, base_offsets, 8 * (n + 1), hipMemcpyHostToDevice, d->stream));
-  if (T) HIP_TRY(hipMemcpyAsync(d_bases, bases, T, hipMemcpyHostToDevice, d->stream));
-  if (T) HIP_TRY(hipMemcpyAsync(d_trans, trans, 4 * T, hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(hipMemcpyAsync(d_nb, nb.data(), 4 * n, hipMemcpyHostToDevice, d->stream));
-  int e = launch_bc_search(d_bases, d_off, d_nb, n_reads, pat, 1, d_best, d->stream);
-  if (!e) e = launch_bc_finalize(d_trans, d_off, d_nb, n_reads, pat, 1, 0, d_best, d_res, d->stream);
-  if (e) { g_hip_error = hipGetErrorString((hipError_t)e); return LVA_ERR_HIP; }
-  HIP_TRY(hipMemcpyAsync(out, d_res, sizeof(BcResult) * n, hipMemcpyDeviceToHost, d->stream));
-  HIP_TRY(hipStreamSynchronize(d->stream));
-  return LVA_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------
-// DESIGN.md section 1 row N3': demultiplexing a pooled run (bc_search_multi, bc_demux_finalize).
-// ---------------------------------------------------------------------------------------------
-namespace {
-
-struct DemuxArgs {
-  std::vector<BcPatterns> pats;
-  std::vector<uint32_t> min_len;
-  int32_t max_dist, min_margin;
-};
-
-// everything that can be refused without the device
-int demux_args(const lva_experiment_barcodes* exps, int32_t n_exps, int32_t max_dist, int32_t min_margin, DemuxArgs* a) {
-  if (!exps || n_exps < 1 || n_exps > kMaxExperiments || min_margin < 0) return LVA_ERR_ARG;
-  a->pats.resize(n_exps);
-  a->min_len.resize(n_exps);
-  for (int32_t e = 0; e < n_exps; ++e) {
-    // both reverse complements are formed: a character outside ACGTN in either barcode is refused here
-    const int st = make_patterns(exps[e].start_barcode, exps[e].end_barcode, 2, &a->pats[e]);
-    if (st != LVA_OK) return st;
-    a->min_len[e] = exps[e].min_len;
-  }
-  a->max_dist = max_dist < 0 ? -1 : max_dist;
-  a->min_margin = min_margin;
-  return LVA_OK;
-}
-
-struct DemuxDev {
-  BcPatterns* pats;
-  uint32_t *min_len, *best;
-  BcDemuxResult* res;
-  BcResult* all;
-};
-
-size_t demux_bytes(size_t n, size_t k, bool all) {
-  return DevBlock::pad(sizeof(BcPatterns) * k) + DevBlock::pad(4 * k) + DevBlock::pad(16 * n * k) +
-         DevBlock::pad(sizeof(BcDemuxResult) * n) + (all ? DevBlock::pad(sizeof(BcResult) * n * k) : 0);
-}
-
-// search + choice on basecalls that are on the device; copies the results out and waits
-int demux_run(lva_decoder* d, DevBlock* blk, const char* d_bases, const uint32_t* d_trans, const int64_t* d_off,
-              const int32_t* d_nb, int32_t n_reads, const DemuxArgs& a, lva_demux_pos* out, lva_payload_pos* all_out) {
-  static_assert(sizeof(lva_demux_pos) == sizeof(BcDemuxResult), "lva_demux_pos layout");
-  const size_t n = (size_t)n_reads, k = a.pats.size();
-  DemuxDev v;
-  v.pats = blk->take<BcPatterns>(k);
-  v.min_len = blk->take<uint32_t>(k);
-  v.best = blk->take<uint32_t>(4 * n * k);
-  v.res = blk->take<BcDemuxResult>(n);
-  v.all = all_out ? blk->take<BcResult>(n * k) : nullptr;
-  HIP_TRY(hipMemcpyAsync(v.pats, a.pats.data(), sizeof(BcPatterns) * k, hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(hipMemcpyAsync(v.min_len, a.min_len.data(), 4 * k, hipMemcpyHostToDevice, d->stream));
-  int e = launch_bc_search_multi(d_bases, d_off, d_nb, n_reads, v.pats, (int32_t)k, v.best, d->stream);
-  if (!e) e = launch_bc_demux_finalize(d_trans, d_off, d_nb, n_reads, v.pats, v.min_len, (int32_t)k, a.max_dist, a.min_margin,
-                                       v.best, v.res, v.all, d->stream);
-  if (e) { g_hip_error = hipGetErrorString((hipError_t)e); (void)hipStreamSynchronize(d->stream); return LVA_ERR_HIP; }
-  HIP_TRY(hipMemcpyAsync(out, v.res, sizeof(BcDemuxResult) * n, hipMemcpyDeviceToHost, d->stream));
-  if (all_out) HIP_TRY(hipMemcpyAsync(all_out, v.all, sizeof(BcResult) * n * k, hipMemcpyDeviceToHost, d->stream));
-  HIP_TRY(hipStreamSynchronize(d->stream));
-  return LVA_OK;
-}
-
-// basecall of resident posteriors, then demux_run
-int demux_post(lva_decoder* d, const float* post_dev, const int64_t* row_offsets, int32_t n, const DemuxArgs& a,
-               lva_demux_pos* out, lva_payload_pos* all_out) {
-  if (row_offsets[0] != 0) return LVA_ERR_ARG;
-  for (int32_t i = 0; i < n; ++i)
-    if (row_offsets[i + 1] < row_offsets[i] || row_offsets[i + 1] - row_offsets[i] > kBcMaxBlocks) return LVA_ERR_ARG;
-  const size_t T = (size_t)row_offsets[n];
-  if (T >= ((size_t)1 << 31)) return LVA_ERR_ARG;          // 32-bit block offsets inside the kernels
-  DevBlock blk;
-  blk.cap = DevBlock::pad(8 * ((size_t)n + 1)) + DevBlock::pad(8 * T + 8) + DevBlock::pad(T + n + 1) + DevBlock::pad(T + 1) +
-            DevBlock::pad(4 * T + 4) + DevBlock::pad(4 * (size_t)n) + demux_bytes(n, a.pats.size(), all_out != nullptr);
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&blk.base), blk.cap));
-  int64_t* d_off = blk.take<int64_t>((size_t)n + 1);
-  uint32_t* d_tb = blk.take<uint32_t>(2 * T);          // 8 back-pointer bytes per block
-  uint8_t* d_path = blk.take<uint8_t>(T + n);
-  char* d_bases = blk.take<char>(T);
-  uint32_t* d_trans = blk.take<uint32_t>(T);
-  int32_t* d_nb = blk.take<int32_t>(n);
-  HIP_TRY(hipMemcpyAsync(d_off, row_offsets, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, d->stream));
-  const int e = launch_bc_basecall(post_dev, d_off, n, d_tb, d_path, d_bases, d_trans, d_nb, d->stream);
-  if (e) { g_hip_error = hipGetErrorString((hipError_t)e); (void)hipStreamSynchronize(d->stream); return LVA_ERR_HIP; }
-  const int st = demux_run(d, &blk, d_bases, d_trans, d_off, d_nb, n, a, out, all_out);
-  if (st != LVA_OK) (void)hipStreamSynchronize(d->stream);     // nothing of blk is in use when it is freed
-  return st;
-}
-
-}  // namespace
-
-extern "C" {
-
-int lva_demux_batch_device(lva_decoder* d, const float* post_dev, const int64_t* row_offsets, int32_t n_reads,
-                           const lva_experiment_barcodes* exps, int32_t n_exps, int32_t max_dist, int32_t min_margin,
-                           lva_demux_pos* out, lva_payload_pos* all_out) {
-  if (!d || n_reads < 0 || !row_offsets || (n_reads > 0 && (!post_dev || !out))) return LVA_ERR_ARG;
-  DemuxArgs a;
-  const int st = demux_args(exps, n_exps, max_dist, min_margin, &a);
-  if (st != LVA_OK) return st;
-  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
-  if (n_reads == 0) return LVA_OK;
-  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
-  return demux_post(d, post_dev, row_offsets, n_reads, a, out, all_out);
-}
-
-int lva_demux_batch(lva_decoder* d, const float* post, const int64_t* row_offsets, int32_t n_reads,
-                    const lva_experiment_barcodes* exps, int32_t n_exps, int32_t max_dist, int32_t min_margin,
-                    lva_demux_pos* out, lva_payload_pos* all_out) {
-  if (!d || n_reads < 0 || !row_offsets || (n_reads > 0 && (!post || !out))) return LVA_ERR_ARG;
-  DemuxArgs a;
-  int st = demux_args(exps, n_exps, max_dist, min_margin, &a);
-  if (st != LVA_OK) return st;
-  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
-  if (n_reads == 0) return LVA_OK;
-  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
-  HostPost hp;
-  st = upload_post(d, post, row_offsets, n_reads, &hp);
-  if (st == LVA_OK) st = demux_post(d, hp.dev, row_offsets, n_reads, a, out, all_out);
-  if (st != LVA_OK) (void)hipStreamSynchronize(d->stream);     // the upload may still be in flight
-  return st;
-}
-
-int lva_demux_bases_batch(lva_decoder* d, const char* bases, const uint32_t* trans, const int64_t* base_offsets,
-                          int32_t n_reads, const lva_experiment_barcodes* exps, int32_t n_exps, int32_t max_dist,
-                          int32_t min_margin, lva_demux_pos* out, lva_payload_pos* all_out) {
-  if (!d || n_reads < 0 || !base_offsets || (n_reads > 0 && (!bases || !trans || !out))) return LVA_ERR_ARG;
-  DemuxArgs a;
-  const int st = demux_args(exps, n_exps, max_dist, min_margin, &a);
-  if (st != LVA_OK) return st;
-  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the slots, the work list and the profile
-  if (n_reads == 0) return LVA_OK;
-  if (base_offsets[0] != 0) return LVA_ERR_ARG;
-  std::vector<int32_t> nb(n_reads);
-  for (int32_t i = 0; i < n_reads; ++i) {
-    if (base_offsets[i + 1] < base_offsets[i] || base_offsets[i + 1] - base_offsets[i] > kBcMaxBlocks) return LVA_ERR_ARG;
-    nb[i] = (int32_t)(base_offsets[i + 1] - base_offsets[i]);
-  }
-  const size_t T = (size_t)base_offsets[n_reads], n = (size_t)n_reads;
-  if (T >= ((size_t)1 << 31)) return LVA_ERR_ARG;
-  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
-  DevBlock blk;
-  blk.cap = DevBlock::pad(8 * (n + 1)) + DevBlock::pad(T + 1) + DevBlock::pad(4 * T + 4) + DevBlock::pad(4 * n) +
-            demux_bytes(n, a.pats.size(), all_out != nullptr);
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&blk.base), blk.cap));
-  int64_t* d_off = blk.take<int64_t>(n + 1);
-  char* d_bases = blk.take<char>(T);
-  uint32_t* d_trans = blk.take<uint32_t>(T);
-  int32_t* d_nb = blk.take<int32_t>(n);
-  int rc = LVA_OK;
-  if (hipMemcpyAsync(d_off, base_offsets, 8 * (n + 1), hipMemcpyHostToDevice, d->stream) != hipSuccess ||
-      (T && hipMemcpyAsync(d_bases, bases, T, hipMemcpyHostToDevice, d->stream) != hipSuccess) ||
-      (T && hipMemcpyAsync(d_trans, trans, 4 * T, hipMemcpyHostToDevice, d->stream) != hipSuccess) ||
-      hipMemcpyAsync(d_nb, nb.data(), 4 * n, hipMemcpyHostToDevice, d->stream) != hipSuccess) {
-    g_hip_error = "hipMemcpyAsync (demultiplexing inputs)";
-    rc = LVA_ERR_HIP;
-  }
-  if (rc == LVA_OK) rc = demux_run(d, &blk, d_bases, d_trans, d_off, d_nb, n_reads, a, out, all_out);
-  if (rc != LVA_OK) (void)hipStreamSynchronize(d->stream);     // nb and blk are released on return
-  return rc;
-}
-
-}  // extern "C"
-
-/* ---------------------------------------------------------------------------------------------
- * the consumers of a decoded list (csrc/ls_kernels.hip).  Like the RS entry
- * points they take a device ordinal, work on a stream of their own and leave every decoder's profile alone.
- * ------------------------------------------------------------------------------------------- */
-namespace {
-
-struct LsStream {               // a stream for the length of one call
-  hipStream_t s = nullptr;
-  ~LsStream() { if (s) (void)hipStreamDestroy(s); }
-};
-
-int ls_open(int32_t device, LsStream* st) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return LVA_ERR_NO_DEVICE;
-  if (hipSetDevice(device) != hipSuccess) return LVA_ERR_NO_DEVICE;
-  HIP_TRY(hipStreamCreateWithFlags(&st->s, hipStreamNonBlocking));
-  return LVA_OK;
-}
-
-// msgs / counts of n reads: the shape every list consumer accepts
-bool ls_shape_ok(int32_t n_reads, int32_t list_size, uint32_t msg_len) {
-  if (n_reads < 0 || list_size < 1 || msg_len < 1 || msg_len > (uint32_t)kLsMaxMsgLen) return false;
-  return (uint64_t)n_reads * (uint64_t)list_size * (uint64_t)msg_len < (1ull << 31);
-}
-
-}  // namespace
-
-extern "C" {
-
-int lva_list_filter(int32_t device, const uint8_t* msgs, const int32_t* counts, int32_t n_reads, int32_t list_size,
-                    uint32_t msg_len, int32_t use_entries, int32_t bytes_per_oligo, int32_t num_oligos, int32_t pad,
-                    int32_t* out_index, int32_t* out_rank, uint8_t* out_payload) {
-  if (!msgs || !counts || !out_index || !out_rank || !out_payload) return LVA_ERR_ARG;
-  if (!ls_shape_ok(n_reads, list_size, msg_len) || use_entries < 0 || use_entries > list_size) return LVA_ERR_ARG;
-  if (bytes_per_oligo < 1 || num_oligos < 1 || num_oligos > 4096) return LVA_ERR_ARG;
-  if ((uint64_t)msg_len != 12ull + 8ull + 8ull * (uint64_t)bytes_per_oligo + (pad ? 1ull : 0ull)) return LVA_ERR_ARG;
-  if (n_reads == 0) return LVA_OK;
-  const int32_t use = use_entries ? use_entries : list_size;
-  LsStream st;
-  const int so = ls_open(device, &st);
-  if (so != LVA_OK) return so;
-  const size_t n = (size_t)n_reads, mb = n * (size_t)list_size * msg_len, pb = n * (size_t)bytes_per_oligo;
-  DevBlock blk;
-  blk.cap = DevBlock::pad(mb) + 3 * DevBlock::pad(4 * n) + DevBlock::pad(pb);
-  if (hipMalloc(reinterpret_cast<void**>(&blk.base), blk.cap) != hipSuccess) return LVA_ERR_NOMEM;
-  uint8_t* d_msgs = blk.take<uint8_t>(mb);               // 256-byte aligned and padded: whole dwords may be read
-  int32_t* d_counts = blk.take<int32_t>(n);
-  int32_t* d_index = blk.take<int32_t>(n);
-  int32_t* d_rank = blk.take<int32_t>(n);
-  uint8_t* d_pay = blk.take<uint8_t>(pb);
-  HIP_TRY(hipMemcpyAsync(d_msgs, msgs, mb, hipMemcpyHostToDevice, st.s));
-  HIP_TRY(hipMemcpyAsync(d_counts, counts, 4 * n, hipMemcpyHostToDevice, st.s));
-  const int e = launch_ls_filter(d_msgs, d_counts, n_reads, list_size, msg_len, use, bytes_per_oligo, num_oligos, pad, d_index,
-                                 d_rank, d_pay, st.s);
-  if (e) { g_hip_error = hipGetErrorString((hipError_t)e); (void)hipStreamSynchronize(st.s); return LVA_ERR_HIP; }
-  HIP_TRY(hipMemcpyAsync(out_index, d_index, 4 * n, hipMemcpyDeviceToHost, st.s));
-  HIP_TRY(hipMemcpyAsync(out_rank, d_rank, 4 * n, hipMemcpyDeviceToHost, st.s));
-  HIP_TRY(hipMemcpyAsync(out_payload, d_pay, pb, hipMemcpyDeviceToHost, st.s));
-  HIP_TRY(hipStreamSynchronize(st.s));
-  return LVA_OK;
-}
-
-int lva_list_consensus(int32_t device, const int32_t* index, const uint8_t* payload, int32_t n_reads, int32_t bytes_per_oligo,
-                       int32_t num_oligos, int32_t first_only, uint8_t* out_present, uint8_t* out_payload, int32_t* out_votes) {
-  if (!index || !payload || !out_present || !out_payload || !out_votes) return LVA_ERR_ARG;
-  if (n_reads < 0 || bytes_per_oligo < 1 || num_oligos < 1 || num_oligos > 4096) return LVA_ERR_ARG;
-  if ((uint64_t)n_reads * (uint64_t)bytes_per_oligo >= (1ull << 31)) return LVA_ERR_ARG;
-  for (int32_t i = 0; i < n_reads; ++i)
-    if (index[i] >= num_oligos) return LVA_ERR_ARG;      // (negative: the read passed no entry and has no vote)
-  if (n_reads == 0) return LVA_OK;
-  LsStream st;
-  const int so = ls_open(device, &st);
-  if (so != LVA_OK) return so;
-  const size_t n = (size_t)n_reads, no = (size_t)num_oligos, pb = n * (size_t)bytes_per_oligo, ob = no * (size_t)bytes_per_oligo;
-  DevBlock blk;
-  blk.cap = 2 * DevBlock::pad(4 * n) + DevBlock::pad(pb) + DevBlock::pad(4 * (no + 1)) + DevBlock::pad(no) + DevBlock::pad(ob) +
-            DevBlock::pad(4 * no);
-  if (hipMalloc(reinterpret_cast<void**>(&blk.base), blk.cap) != hipSuccess) return LVA_ERR_NOMEM;
-  int32_t* d_index = blk.take<int32_t>(n);
-  int32_t* d_order = blk.take<int32_t>(n);
-  uint8_t* d_pay = blk.take<uint8_t>(pb);
-  int32_t* d_bucket = blk.take<int32_t>(no + 1);
-  uint8_t* d_present = blk.take<uint8_t>(no);
-  uint8_t* d_out = blk.take<uint8_t>(ob);
-  int32_t* d_votes = blk.take<int32_t>(no);
-  HIP_TRY(hipMemcpyAsync(d_index, index, 4 * n, hipMemcpyHostToDevice, st.s));
-  HIP_TRY(hipMemcpyAsync(d_pay, payload, pb, hipMemcpyHostToDevice, st.s));
-  const int e = launch_ls_consensus(d_index, d_pay, n_reads, bytes_per_oligo, num_oligos, first_only ? 1 : 0, d_bucket, d_order,
-                                    d_present, d_out, d_votes, st.s);
-  if (e) { g_hip_error = hipGetErrorString((hipError_t)e); (void)hipStreamSynchronize(st.s); return LVA_ERR_HIP; }
-  HIP_TRY(hipMemcpyAsync(out_present, d_present, no, hipMemcpyDeviceToHost, st.s));
-  HIP_TRY(hipMemcpyAsync(out_payload, d_out, ob, hipMemcpyDeviceToHost, st.s));
-  HIP_TRY(hipMemcpyAsync(out_votes, d_votes, 4 * no, hipMemcpyDeviceToHost, st.s));
-  HIP_TRY(hipStreamSynchronize(st.s));
-  return LVA_OK;
-}
-
-int lva_list_stats(int32_t device, const uint8_t* msgs, const int32_t* counts, const uint8_t* truth, int32_t n_reads,
-                   int32_t list_size, uint32_t msg_len, lva_list_stat* out) {
-  static_assert(sizeof(lva_list_stat) == kLsStatFields * sizeof(int32_t), "ls_stats writes the fields of lva_list_stat in order");
-  if (!msgs || !counts || !truth || !out) return LVA_ERR_ARG;
-  if (!ls_shape_ok(n_reads, list_size, msg_len)) return LVA_ERR_ARG;
-  if (n_reads == 0) return LVA_OK;
-  LsStream st;
-  const int so = ls_open(device, &st);
-  if (so != LVA_OK) return so;
-  const size_t n = (size_t)n_reads, mb = n * (size_t)list_size * msg_len, tb = n * msg_len;
-  DevBlock blk;
-  blk.cap = DevBlock::pad(mb) + DevBlock::pad(4 * n) + DevBlock::pad(tb) + DevBlock::pad(8 * kLsPackWords * n) +
-            DevBlock::pad(4 * kLsStatFields * n);
-  if (hipMalloc(reinterpret_cast<void**>(&blk.base), blk.cap) != hipSuccess) return LVA_ERR_NOMEM;
-  uint8_t* d_msgs = blk.take<uint8_t>(mb);
-  int32_t* d_counts = blk.take<int32_t>(n);
-  uint8_t* d_truth = blk.take<uint8_t>(tb);
-  uint64_t* d_packed = blk.take<uint64_t>(kLsPackWords * n);
-  int32_t* d_out = blk.take<int32_t>(kLsStatFields * n);
-  HIP_TRY(hipMemcpyAsync(d_msgs, msgs, mb, hipMemcpyHostToDevice, st.s));
-  HIP_TRY(hipMemcpyAsync(d_counts, counts, 4 * n, hipMemcpyHostToDevice, st.s));
-  HIP_TRY(hipMemcpyAsync(d_truth, truth, tb, hipMemcpyHostToDevice, st.s));
-  const int e = launch_ls_stats(d_msgs, d_counts, d_truth, n_reads, list_size, msg_len, d_packed, d_out, st.s);
-  if (e) { g_hip_error = hipGetErrorString((hipError_t)e); (void)hipStreamSynchronize(st.s); return LVA_ERR_HIP; }
-  HIP_TRY(hipMemcpyAsync(out, d_out, 4 * kLsStatFields * n, hipMemcpyDeviceToHost, st.s));
-  HIP_TRY(hipStreamSynchronize(st.s));
   return LVA_OK;
 }
 

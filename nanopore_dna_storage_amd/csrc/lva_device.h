@@ -1,4 +1,4 @@
-// lva_device.h -- structures shared by the host driver (lva_api.cpp) and the HIP kernels.
+// lva_device.h -- structures shared by the host driver (lva_api.cpp; lva_host.h carries them to lva_stages.cpp) and the HIP kernels.
 //
 // Trellis memory (HBM), per read slot:
 //     block[parity 2][ring R][crf 8][list L]   each block = 1+P planes of N conv states x 8 bytes:

@@ -1,0 +1,553 @@
+// lva_stages.cpp -- C ABI (include/lva_decoder.h) of the stages beside the list decoder: transition posteriors (N0), basecall
+// and barcode localisation (N3), demultiplexing (N3'), the consumers of a decoded list (N2).  No algorithm lives here: an entry
+// point checks its arguments, declares its device pieces, uploads, launches, copies back and waits, all through the functions below.
+#include <algorithm>
+#include <cstring>
+
+#include "lva_host.h"
+#include "bc_kernels.h"
+#include "tp_kernels.h"
+#include "ls_kernels.h"
+
+using namespace lva;
+
+namespace {
+
+// bc_search packs (edit distance << 20 | window index) into one word for its minimum reduction
+// (bc_kernels.hip): a read may have at most 2^20 blocks / called bases.  Real reads have a few thousand.
+constexpr int64_t kBcMaxBlocks = (int64_t)1 << 20;
+
+// THE validation of a ragged batch, from the offsets alone: first offset 0, non-decreasing, at most kBcMaxBlocks per
+// read, fewer than 2^31 in all (32-bit block offsets inside the kernels).  Every entry point that takes row_offsets or
+// base_offsets calls it before it allocates or copies anything; *total = offsets[n].
+int check_offsets(const int64_t* offsets, int32_t n, size_t* total) {
+  *total = 0;
+  if (n == 0) return LVA_OK;
+  if (offsets[0] != 0) return LVA_ERR_ARG;
+  for (int32_t i = 0; i < n; ++i)
+    if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > kBcMaxBlocks) return LVA_ERR_ARG;
+  if (offsets[n] >= ((int64_t)1 << 31)) return LVA_ERR_ARG;
+  *total = (size_t)offsets[n];
+  return LVA_OK;
+}
+
+// per-read counts of a batch that check_offsets has passed
+std::vector<int32_t> read_lengths(const int64_t* offsets, int32_t n) {
+  std::vector<int32_t> len((size_t)n);
+  for (int32_t i = 0; i < n; ++i) len[i] = (int32_t)(offsets[i + 1] - offsets[i]);
+  return len;
+}
+
+// What every decoder-bound stage does once its own arguments, its barcodes and its offsets have passed (an argument
+// error wins over an open stream): busy, nothing to do, device -- in this order.  kRun: there is work, the device is set.
+constexpr int kRun = 1;
+int stage_enter(lva_decoder* d, bool empty) {
+  if (d->open_stream) return LVA_ERR_BUSY;   // a stream owns the decoder's HIP stream, the slots and the profile
+  if (empty) return LVA_OK;
+  if (hipSetDevice(d->device) != hipSuccess) return LVA_ERR_NO_DEVICE;
+  return kRun;
+}
+int stage_enter(lva_decoder* d, const int64_t* offsets, int32_t n, size_t* total) {     // the offsets, then the above
+  return check_offsets(offsets, n, total) != LVA_OK ? LVA_ERR_ARG : stage_enter(d, n == 0);
+}
+
+// One device allocation for the length of a call, carved into 256-byte aligned and padded pieces.  The pieces are
+// declared first (add), alloc() sizes the block from what was declared, ptr() hands them out: the capacity cannot
+// disagree with the pieces.  Declare it before the call's StreamDrain, so that it is freed behind the drain.
+class Arena {
+  static constexpr size_t kAbsent = ~(size_t)0;
+
+ public:
+  template <typename T> struct Piece { size_t at = kAbsent; };   // default: a piece that was not asked for, ptr() = null
+  Arena() = default;
+  Arena(const Arena&) = delete;
+  ~Arena() { if (base_) (void)hipFree(base_); }
+  // a piece of count 0 still occupies one padded unit; ls_filter reads whole dwords up to the padded end of its messages
+  template <typename T> Piece<T> add(size_t count) {
+    Piece<T> p;
+    p.at = size_;
+    size_ += (std::max<size_t>(count, 1) * sizeof(T) + 255) & ~(size_t)255;
+    return p;
+  }
+  int alloc() { return hipMalloc(reinterpret_cast<void**>(&base_), size_) == hipSuccess ? LVA_OK : LVA_ERR_NOMEM; }
+  template <typename T> T* ptr(Piece<T> p) const { return p.at == kAbsent ? nullptr : reinterpret_cast<T*>(base_ + p.at); }
+
+ private:
+  char* base_ = nullptr;
+  size_t size_ = 0;
+};
+
+int upload_post(lva_decoder* d, const float* post, size_t blocks, HostPost* hp) {     // blocks: check_offsets' total
+  if (hipMalloc(reinterpret_cast<void**>(&hp->dev), std::max<size_t>(blocks, 1) * 160) != hipSuccess) return LVA_ERR_NOMEM;
+  if (blocks > 0) HIP_TRY(hipMemcpyAsync(hp->dev, post, blocks * 160, hipMemcpyHostToDevice, d->stream));
+  return LVA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// basecall of the posterior matrix and barcode localisation.
+// ---------------------------------------------------------------------------------------------
+
+bool rc_pattern(const char* src, int len, char* dst) {        // helper.reverse_complement (helper.py:227-229)
+  for (int i = 0; i < len; ++i) {
+    char c;
+    switch (src[len - 1 - i]) {
+      case 'A': c = 'T'; break;
+      case 'C': c = 'G'; break;
+      case 'G': c = 'C'; break;
+      case 'T': c = 'A'; break;
+      case 'N': c = 'N'; break;
+      default: return false;
+    }
+    dst[i] = c;
+  }
+  return true;
+}
+
+int make_patterns(const char* start_bc, const char* end_bc, int n_orient, BcPatterns* p) {
+  if (!start_bc || !end_bc) return LVA_ERR_ARG;
+  const size_t ls = std::strlen(start_bc), le = std::strlen(end_bc);
+  if (ls == 0 || le == 0 || ls > (size_t)kMaxBarcode || le > (size_t)kMaxBarcode) return LVA_ERR_ARG;
+  std::memset(p, 0, sizeof *p);
+  p->len[0] = (uint8_t)ls; p->len[1] = (uint8_t)le;
+  std::memcpy(p->pat[0], start_bc, ls);
+  std::memcpy(p->pat[1], end_bc, le);
+  if (n_orient == 2) {         // generate_decoded_lists.py:33-34: START_BARCODE_RC = rc(END), END_BARCODE_RC = rc(START)
+    p->len[2] = (uint8_t)le; p->len[3] = (uint8_t)ls;
+    if (!rc_pattern(end_bc, (int)le, p->pat[2]) || !rc_pattern(start_bc, (int)ls, p->pat[3])) return LVA_ERR_ARG;
+  }
+  return LVA_OK;
+}
+
+// Basecalls of n reads (T blocks or bases in all) on the device, as the searches read them: made there by bc_basecall
+// (basecall_set: its working set) or the caller's own, uploaded (given_set).  Declaration order = order in the block.
+struct Calls {
+  Arena::Piece<int64_t> off;
+  Arena::Piece<uint32_t> tb;     // 8 back-pointer bytes per block
+  Arena::Piece<uint8_t> path;
+  Arena::Piece<char> bases;
+  Arena::Piece<uint32_t> trans;
+  Arena::Piece<int32_t> nb;
+};
+Calls basecall_set(Arena& a, size_t n, size_t T) {
+  return {a.add<int64_t>(n + 1), a.add<uint32_t>(2 * T), a.add<uint8_t>(T + n), a.add<char>(T), a.add<uint32_t>(T), a.add<int32_t>(n)};
+}
+
+Calls given_set(Arena& a, size_t n, size_t T) {
+  return {a.add<int64_t>(n + 1), {}, {}, a.add<char>(T), a.add<uint32_t>(T), a.add<int32_t>(n)};
+}
+
+// offsets up, bc_basecall over posteriors that are on the device
+int enqueue_basecall(lva_decoder* d, const Arena& a, const Calls& c, const float* post_dev, const int64_t* row_offsets, int32_t n) {
+  HIP_TRY(hipMemcpyAsync(a.ptr(c.off), row_offsets, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, d->stream));
+  return launch_status(launch_bc_basecall(post_dev, a.ptr(c.off), n, a.ptr(c.tb), a.ptr(c.path), a.ptr(c.bases), a.ptr(c.trans),
+                                          a.ptr(c.nb), d->stream));
+}
+
+// the caller's basecalls up; nb (read_lengths) outlives the call's StreamDrain
+int enqueue_given(lva_decoder* d, const Arena& a, const Calls& c, const char* bases, const uint32_t* trans,
+                  const int64_t* base_offsets, const std::vector<int32_t>& nb, size_t T) {
+  const size_t n = nb.size();
+  HIP_TRY(hipMemcpyAsync(a.ptr(c.off), base_offsets, 8 * (n + 1), hipMemcpyHostToDevice, d->stream));
+  if (T) HIP_TRY(hipMemcpyAsync(a.ptr(c.bases), bases, T, hipMemcpyHostToDevice, d->stream));
+  if (T) HIP_TRY(hipMemcpyAsync(a.ptr(c.trans), trans, 4 * T, hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(a.ptr(c.nb), nb.data(), 4 * n, hipMemcpyHostToDevice, d->stream));
+  return LVA_OK;
+}
+
+struct LocateSet { Arena::Piece<uint32_t> best; Arena::Piece<BcResult> res; };
+LocateSet locate_set(Arena& a, size_t n) { return {a.add<uint32_t>(4 * n), a.add<BcResult>(n)}; }
+
+// bc_search + bc_finalize over basecalls that are on the device, and the copy of the windows to the caller
+int enqueue_locate(lva_decoder* d, const Arena& a, const Calls& c, const LocateSet& s, int32_t n, const BcPatterns& pat,
+                   int n_orient, uint32_t min_len, lva_payload_pos* out) {
+  static_assert(sizeof(lva_payload_pos) == sizeof(BcResult), "lva_payload_pos layout");
+  int e = launch_bc_search(a.ptr(c.bases), a.ptr(c.off), a.ptr(c.nb), n, pat, n_orient, a.ptr(s.best), d->stream);
+  if (!e) e = launch_bc_finalize(a.ptr(c.trans), a.ptr(c.off), a.ptr(c.nb), n, pat, n_orient, min_len, a.ptr(s.best), a.ptr(s.res),
+                                 d->stream);
+  if (e) return launch_status(e);
+  HIP_TRY(hipMemcpyAsync(out, a.ptr(s.res), sizeof(BcResult) * (size_t)n, hipMemcpyDeviceToHost, d->stream));
+  return LVA_OK;
+}
+
+// lva_basecall_batch[_device] (n_orient = 0: no barcodes, pos_out null) and lva_locate_payload_batch[_device]
+// (n_orient = 2); post is the caller's host buffer or the caller's device buffer
+int basecall_stage(lva_decoder* d, const float* post, bool post_on_host, const int64_t* row_offsets, int32_t n,
+                   const char* start_bc, const char* end_bc, int n_orient, uint32_t min_len, char* bases_out,
+                   uint32_t* trans_out, int32_t* nbases_out, lva_payload_pos* pos_out) {
+  if (!d || n < 0 || !row_offsets || (n > 0 && (!post || (n_orient ? !pos_out : !nbases_out)))) return LVA_ERR_ARG;
+  BcPatterns pat;
+  if (n_orient && make_patterns(start_bc, end_bc, n_orient, &pat) != LVA_OK) return LVA_ERR_ARG;
+  size_t T = 0;
+  int st = stage_enter(d, row_offsets, n, &T);
+  if (st != kRun) return st;
+  Arena arena;
+  HostPost hp;
+  const Calls bc = basecall_set(arena, (size_t)n, T);
+  const LocateSet loc = locate_set(arena, (size_t)n);
+  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
+  StreamDrain drain(d->stream);
+  if (post_on_host && (st = upload_post(d, post, T, &hp)) != LVA_OK) return st;
+  if ((st = enqueue_basecall(d, arena, bc, post_on_host ? hp.dev : post, row_offsets, n)) != LVA_OK) return st;
+  if (n_orient && (st = enqueue_locate(d, arena, bc, loc, n, pat, n_orient, min_len, pos_out)) != LVA_OK) return st;
+  if (bases_out && T) HIP_TRY(hipMemcpyAsync(bases_out, arena.ptr(bc.bases), T, hipMemcpyDeviceToHost, d->stream));
+  if (trans_out && T) HIP_TRY(hipMemcpyAsync(trans_out, arena.ptr(bc.trans), 4 * T, hipMemcpyDeviceToHost, d->stream));
+  if (nbases_out) HIP_TRY(hipMemcpyAsync(nbases_out, arena.ptr(bc.nb), 4 * (size_t)n, hipMemcpyDeviceToHost, d->stream));
+  return drain.finish();
+}
+
+}  // namespace
+
+extern "C" {
+
+int lva_basecall_batch_device(lva_decoder* d, const float* post_dev, const int64_t* row_offsets, int32_t n_reads, char* bases_out,
+                              uint32_t* trans_out, int32_t* nbases_out) {
+  return basecall_stage(d, post_dev, false, row_offsets, n_reads, nullptr, nullptr, 0, 0, bases_out, trans_out, nbases_out, nullptr);
+}
+
+int lva_basecall_batch(lva_decoder* d, const float* post, const int64_t* row_offsets, int32_t n_reads, char* bases_out,
+                       uint32_t* trans_out, int32_t* nbases_out) {
+  return basecall_stage(d, post, true, row_offsets, n_reads, nullptr, nullptr, 0, 0, bases_out, trans_out, nbases_out, nullptr);
+}
+
+int lva_locate_payload_batch_device(lva_decoder* d, const float* post_dev, const int64_t* row_offsets, int32_t n_reads,
+                                    const char* start_barcode, const char* end_barcode, uint32_t min_len, lva_payload_pos* out) {
+  return basecall_stage(d, post_dev, false, row_offsets, n_reads, start_barcode, end_barcode, 2, min_len, nullptr, nullptr, nullptr, out);
+}
+
+int lva_locate_payload_batch(lva_decoder* d, const float* post, const int64_t* row_offsets, int32_t n_reads,
+                             const char* start_barcode, const char* end_barcode, uint32_t min_len, lva_payload_pos* out) {
+  return basecall_stage(d, post, true, row_offsets, n_reads, start_barcode, end_barcode, 2, min_len, nullptr, nullptr, nullptr, out);
+}
+
+int lva_find_barcode_batch(lva_decoder* d, const char* bases, const uint32_t* trans, const int64_t* base_offsets,
+                           int32_t n_reads, const char* start_barcode, const char* end_barcode, lva_payload_pos* out) {
+  if (!d || n_reads < 0 || !base_offsets || (n_reads > 0 && (!bases || !trans || !out))) return LVA_ERR_ARG;
+  BcPatterns pat;
+  if (make_patterns(start_barcode, end_barcode, 1, &pat) != LVA_OK) return LVA_ERR_ARG;
+  size_t T = 0;
+  int st = stage_enter(d, base_offsets, n_reads, &T);
+  if (st != kRun) return st;
+  const std::vector<int32_t> nb = read_lengths(base_offsets, n_reads);
+  Arena arena;
+  const Calls calls = given_set(arena, nb.size(), T);
+  const LocateSet loc = locate_set(arena, nb.size());
+  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
+  StreamDrain drain(d->stream);
+  if ((st = enqueue_given(d, arena, calls, bases, trans, base_offsets, nb, T)) != LVA_OK) return st;
+  if ((st = enqueue_locate(d, arena, calls, loc, n_reads, pat, 1, 0, out)) != LVA_OK) return st;
+  return drain.finish();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// transition posteriors from a network's transition scores.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// forward and backward kernel over n reads resident on the device; post_dev may be scores_dev.  Enqueues only.
+int tp_run(lva_decoder* d, const float* scores_dev, const int64_t* row_offsets, int32_t n, size_t T, float* post_dev) {
+  if (T > d->tp_fwd_cap) {
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    if (d->d_tp_fwd) (void)hipFree(d->d_tp_fwd);
+    d->d_tp_fwd = nullptr; d->tp_fwd_cap = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&d->d_tp_fwd), T * 8 * sizeof(float)) != hipSuccess) return LVA_ERR_NOMEM;
+    d->tp_fwd_cap = T;
+  }
+  if ((size_t)n + 1 > d->tp_off_cap) {
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    if (d->d_tp_off) (void)hipFree(d->d_tp_off);
+    d->d_tp_off = nullptr; d->tp_off_cap = 0;
+    const size_t cap = std::max<size_t>((size_t)n + 1, 1024);
+    if (hipMalloc(reinterpret_cast<void**>(&d->d_tp_off), cap * sizeof(int64_t)) != hipSuccess) return LVA_ERR_NOMEM;
+    d->tp_off_cap = cap;
+  }
+  HIP_TRY(hipMemcpyAsync(d->d_tp_off, row_offsets, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipEventRecord(d->ev_total0, d->stream));
+  int e = launch_tp_forward(scores_dev, d->d_tp_off, n, d->d_tp_fwd, d->stream);
+  if (!e) e = launch_tp_backward(scores_dev, d->d_tp_off, n, d->d_tp_fwd, post_dev, d->stream);
+  if (e) return launch_status(e);
+  HIP_TRY(hipEventRecord(d->ev_total1, d->stream));
+  return LVA_OK;
+}
+
+// the profile after a posterior call: the two kernels' HIP-event time and the blocks they covered
+int tp_profile(lva_decoder* d, size_t T, bool timed) {
+  const int32_t slots = d->prof.slots, kernel = d->prof.kernel;
+  d->prof = lva_profile{};
+  d->prof.slots = slots; d->prof.kernel = kernel;
+  d->prof.read_steps = T;
+  float ms = 0;
+  if (timed) HIP_TRY(hipEventElapsedTime(&ms, d->ev_total0, d->ev_total1));
+  d->prof.total_ms = ms;
+  return LVA_OK;
+}
+
+// lva_transpost_batch (scores and post on the host: the kernels run in place on the device copy) and
+// lva_transpost_batch_device (both the caller's device buffers, which may be one).  A call with no block resets the profile.
+int transpost_stage(lva_decoder* d, const float* scores, bool on_host, const int64_t* row_offsets, int32_t n, float* post) {
+  if (!d || n < 0 || !row_offsets) return LVA_ERR_ARG;
+  size_t T = 0;
+  if (check_offsets(row_offsets, n, &T) != LVA_OK) return LVA_ERR_ARG;
+  // (device buffers: 16-byte row requests)
+  if (T > 0 && (!scores || !post || (!on_host && (((uintptr_t)scores | (uintptr_t)post) & 15u)))) return LVA_ERR_ARG;
+  int st = stage_enter(d, T == 0);
+  if (st == LVA_OK) return tp_profile(d, 0, false);
+  if (st != kRun) return st;
+  HostPost hp;
+  StreamDrain drain(d->stream);              // the offsets are copied from the caller's memory
+  if (on_host && (st = upload_post(d, scores, T, &hp)) != LVA_OK) return st;
+  st = on_host ? tp_run(d, hp.dev, row_offsets, n, T, hp.dev) : tp_run(d, scores, row_offsets, n, T, post);
+  if (st != LVA_OK) return st;
+  if (on_host) HIP_TRY(hipMemcpyAsync(post, hp.dev, T * 160, hipMemcpyDeviceToHost, d->stream));
+  if ((st = drain.finish()) != LVA_OK) return st;
+  return tp_profile(d, T, true);
+}
+
+}  // namespace
+
+extern "C" {
+
+int lva_transpost_batch_device(lva_decoder* d, const float* scores_dev, const int64_t* row_offsets, int32_t n_reads, float* post_dev) {
+  return transpost_stage(d, scores_dev, false, row_offsets, n_reads, post_dev);
+}
+
+int lva_transpost_batch(lva_decoder* d, const float* scores, const int64_t* row_offsets, int32_t n_reads, float* post_out) {
+  return transpost_stage(d, scores, true, row_offsets, n_reads, post_out);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// DESIGN.md section 1 row N3': demultiplexing a pooled run (bc_search_multi, bc_demux_finalize).
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+struct DemuxArgs {
+  std::vector<BcPatterns> pats;
+  std::vector<uint32_t> min_len;
+  int32_t max_dist, min_margin;
+};
+
+// everything that can be refused without the device
+int demux_args(const lva_experiment_barcodes* exps, int32_t n_exps, int32_t max_dist, int32_t min_margin, DemuxArgs* a) {
+  if (!exps || n_exps < 1 || n_exps > kMaxExperiments || min_margin < 0) return LVA_ERR_ARG;
+  a->pats.resize(n_exps);
+  a->min_len.resize(n_exps);
+  for (int32_t e = 0; e < n_exps; ++e) {
+    // both reverse complements are formed: a character outside ACGTN in either barcode is refused here
+    if (make_patterns(exps[e].start_barcode, exps[e].end_barcode, 2, &a->pats[e]) != LVA_OK) return LVA_ERR_ARG;
+    a->min_len[e] = exps[e].min_len;
+  }
+  a->max_dist = max_dist < 0 ? -1 : max_dist;
+  a->min_margin = min_margin;
+  return LVA_OK;
+}
+
+struct DemuxSet {
+  Arena::Piece<BcPatterns> pats;
+  Arena::Piece<uint32_t> min_len;
+  Arena::Piece<uint32_t> best;
+  Arena::Piece<BcDemuxResult> res;
+  Arena::Piece<BcResult> all;    // only when the caller asks for every experiment's candidate
+};
+DemuxSet demux_set(Arena& a, size_t n, size_t k, bool all) {
+  return {a.add<BcPatterns>(k), a.add<uint32_t>(k), a.add<uint32_t>(4 * n * k), a.add<BcDemuxResult>(n),
+          all ? a.add<BcResult>(n * k) : Arena::Piece<BcResult>{}};
+}
+
+// search + choice over basecalls that are on the device, and the copies of the results to the caller; x (demux_args)
+// outlives the call's StreamDrain
+int enqueue_demux(lva_decoder* d, const Arena& a, const Calls& c, const DemuxSet& s, int32_t n_reads, const DemuxArgs& x,
+                  lva_demux_pos* out, lva_payload_pos* all_out) {
+  static_assert(sizeof(lva_demux_pos) == sizeof(BcDemuxResult), "lva_demux_pos layout");
+  const size_t n = (size_t)n_reads, k = x.pats.size();
+  HIP_TRY(hipMemcpyAsync(a.ptr(s.pats), x.pats.data(), sizeof(BcPatterns) * k, hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(a.ptr(s.min_len), x.min_len.data(), 4 * k, hipMemcpyHostToDevice, d->stream));
+  int e = launch_bc_search_multi(a.ptr(c.bases), a.ptr(c.off), a.ptr(c.nb), n_reads, a.ptr(s.pats), (int32_t)k, a.ptr(s.best), d->stream);
+  if (!e) e = launch_bc_demux_finalize(a.ptr(c.trans), a.ptr(c.off), a.ptr(c.nb), n_reads, a.ptr(s.pats), a.ptr(s.min_len), (int32_t)k,
+                                       x.max_dist, x.min_margin, a.ptr(s.best), a.ptr(s.res), a.ptr(s.all), d->stream);
+  if (e) return launch_status(e);
+  HIP_TRY(hipMemcpyAsync(out, a.ptr(s.res), sizeof(BcDemuxResult) * n, hipMemcpyDeviceToHost, d->stream));
+  if (all_out) HIP_TRY(hipMemcpyAsync(all_out, a.ptr(s.all), sizeof(BcResult) * n * k, hipMemcpyDeviceToHost, d->stream));
+  return LVA_OK;
+}
+
+// lva_demux_batch (post on the host) and lva_demux_batch_device: basecall, then search + choice
+int demux_stage(lva_decoder* d, const float* post, bool post_on_host, const int64_t* row_offsets, int32_t n,
+                const lva_experiment_barcodes* exps, int32_t n_exps, int32_t max_dist, int32_t min_margin, lva_demux_pos* out,
+                lva_payload_pos* all_out) {
+  if (!d || n < 0 || !row_offsets || (n > 0 && (!post || !out))) return LVA_ERR_ARG;
+  DemuxArgs x;
+  if (demux_args(exps, n_exps, max_dist, min_margin, &x) != LVA_OK) return LVA_ERR_ARG;
+  size_t T = 0;
+  int st = stage_enter(d, row_offsets, n, &T);
+  if (st != kRun) return st;
+  Arena arena;
+  HostPost hp;
+  const Calls bc = basecall_set(arena, (size_t)n, T);
+  const DemuxSet dm = demux_set(arena, (size_t)n, x.pats.size(), all_out != nullptr);
+  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
+  StreamDrain drain(d->stream);
+  if (post_on_host && (st = upload_post(d, post, T, &hp)) != LVA_OK) return st;
+  if ((st = enqueue_basecall(d, arena, bc, post_on_host ? hp.dev : post, row_offsets, n)) != LVA_OK) return st;
+  if ((st = enqueue_demux(d, arena, bc, dm, n, x, out, all_out)) != LVA_OK) return st;
+  return drain.finish();
+}
+
+}  // namespace
+
+extern "C" {
+
+int lva_demux_batch_device(lva_decoder* d, const float* post_dev, const int64_t* row_offsets, int32_t n_reads,
+                           const lva_experiment_barcodes* exps, int32_t n_exps, int32_t max_dist, int32_t min_margin,
+                           lva_demux_pos* out, lva_payload_pos* all_out) {
+  return demux_stage(d, post_dev, false, row_offsets, n_reads, exps, n_exps, max_dist, min_margin, out, all_out);
+}
+
+int lva_demux_batch(lva_decoder* d, const float* post, const int64_t* row_offsets, int32_t n_reads,
+                    const lva_experiment_barcodes* exps, int32_t n_exps, int32_t max_dist, int32_t min_margin,
+                    lva_demux_pos* out, lva_payload_pos* all_out) {
+  return demux_stage(d, post, true, row_offsets, n_reads, exps, n_exps, max_dist, min_margin, out, all_out);
+}
+
+int lva_demux_bases_batch(lva_decoder* d, const char* bases, const uint32_t* trans, const int64_t* base_offsets,
+                          int32_t n_reads, const lva_experiment_barcodes* exps, int32_t n_exps, int32_t max_dist,
+                          int32_t min_margin, lva_demux_pos* out, lva_payload_pos* all_out) {
+  if (!d || n_reads < 0 || !base_offsets || (n_reads > 0 && (!bases || !trans || !out))) return LVA_ERR_ARG;
+  DemuxArgs x;
+  if (demux_args(exps, n_exps, max_dist, min_margin, &x) != LVA_OK) return LVA_ERR_ARG;
+  size_t T = 0;
+  int st = stage_enter(d, base_offsets, n_reads, &T);
+  if (st != kRun) return st;
+  const std::vector<int32_t> nb = read_lengths(base_offsets, n_reads);
+  Arena arena;
+  const Calls calls = given_set(arena, nb.size(), T);
+  const DemuxSet dm = demux_set(arena, nb.size(), x.pats.size(), all_out != nullptr);
+  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
+  StreamDrain drain(d->stream);
+  if ((st = enqueue_given(d, arena, calls, bases, trans, base_offsets, nb, T)) != LVA_OK) return st;
+  if ((st = enqueue_demux(d, arena, calls, dm, n_reads, x, out, all_out)) != LVA_OK) return st;
+  return drain.finish();
+}
+
+}  // extern "C"
+
+/* ---------------------------------------------------------------------------------------------
+ * the consumers of a decoded list (csrc/ls_kernels.hip).  Like the RS entry
+ * points they take a device ordinal, work on a stream of their own and leave every decoder's profile alone.
+ * Arguments first, then the device ordinal.
+ * ------------------------------------------------------------------------------------------- */
+namespace {
+
+struct LsStream {               // a stream for the length of one call
+  hipStream_t s = nullptr;
+  ~LsStream() { if (s) (void)hipStreamDestroy(s); }
+};
+
+int ls_open(int32_t device, LsStream* st) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return LVA_ERR_NO_DEVICE;
+  if (hipSetDevice(device) != hipSuccess) return LVA_ERR_NO_DEVICE;
+  HIP_TRY(hipStreamCreateWithFlags(&st->s, hipStreamNonBlocking));
+  return LVA_OK;
+}
+
+// msgs / counts of n reads: the shape every list consumer accepts
+bool ls_shape_ok(int32_t n_reads, int32_t list_size, uint32_t msg_len) {
+  if (n_reads < 0 || list_size < 1 || msg_len < 1 || msg_len > (uint32_t)kLsMaxMsgLen) return false;
+  return (uint64_t)n_reads * (uint64_t)list_size * (uint64_t)msg_len < (1ull << 31);
+}
+
+}  // namespace
+
+extern "C" {
+
+int lva_list_filter(int32_t device, const uint8_t* msgs, const int32_t* counts, int32_t n_reads, int32_t list_size,
+                    uint32_t msg_len, int32_t use_entries, int32_t bytes_per_oligo, int32_t num_oligos, int32_t pad,
+                    int32_t* out_index, int32_t* out_rank, uint8_t* out_payload) {
+  if (!msgs || !counts || !out_index || !out_rank || !out_payload) return LVA_ERR_ARG;
+  if (!ls_shape_ok(n_reads, list_size, msg_len) || use_entries < 0 || use_entries > list_size) return LVA_ERR_ARG;
+  if (bytes_per_oligo < 1 || num_oligos < 1 || num_oligos > 4096) return LVA_ERR_ARG;
+  if ((uint64_t)msg_len != 12ull + 8ull + 8ull * (uint64_t)bytes_per_oligo + (pad ? 1ull : 0ull)) return LVA_ERR_ARG;
+  if (n_reads == 0) return LVA_OK;
+  const int32_t use = use_entries ? use_entries : list_size;
+  LsStream st;
+  if (const int so = ls_open(device, &st)) return so;
+  const size_t n = (size_t)n_reads, mb = n * (size_t)list_size * msg_len, pb = n * (size_t)bytes_per_oligo;
+  Arena arena;
+  const auto d_msgs = arena.add<uint8_t>(mb);            // 256-byte aligned and padded: whole dwords may be read
+  const auto d_counts = arena.add<int32_t>(n), d_index = arena.add<int32_t>(n), d_rank = arena.add<int32_t>(n);
+  const auto d_pay = arena.add<uint8_t>(pb);
+  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
+  StreamDrain drain(st.s);
+  HIP_TRY(hipMemcpyAsync(arena.ptr(d_msgs), msgs, mb, hipMemcpyHostToDevice, st.s));
+  HIP_TRY(hipMemcpyAsync(arena.ptr(d_counts), counts, 4 * n, hipMemcpyHostToDevice, st.s));
+  const int e = launch_ls_filter(arena.ptr(d_msgs), arena.ptr(d_counts), n_reads, list_size, msg_len, use, bytes_per_oligo, num_oligos,
+                                 pad, arena.ptr(d_index), arena.ptr(d_rank), arena.ptr(d_pay), st.s);
+  if (e) return launch_status(e);
+  HIP_TRY(hipMemcpyAsync(out_index, arena.ptr(d_index), 4 * n, hipMemcpyDeviceToHost, st.s));
+  HIP_TRY(hipMemcpyAsync(out_rank, arena.ptr(d_rank), 4 * n, hipMemcpyDeviceToHost, st.s));
+  HIP_TRY(hipMemcpyAsync(out_payload, arena.ptr(d_pay), pb, hipMemcpyDeviceToHost, st.s));
+  return drain.finish();
+}
+
+int lva_list_consensus(int32_t device, const int32_t* index, const uint8_t* payload, int32_t n_reads, int32_t bytes_per_oligo,
+                       int32_t num_oligos, int32_t first_only, uint8_t* out_present, uint8_t* out_payload, int32_t* out_votes) {
+  if (!index || !payload || !out_present || !out_payload || !out_votes) return LVA_ERR_ARG;
+  if (n_reads < 0 || bytes_per_oligo < 1 || num_oligos < 1 || num_oligos > 4096) return LVA_ERR_ARG;
+  if ((uint64_t)n_reads * (uint64_t)bytes_per_oligo >= (1ull << 31)) return LVA_ERR_ARG;
+  for (int32_t i = 0; i < n_reads; ++i)
+    if (index[i] >= num_oligos) return LVA_ERR_ARG;      // (negative: the read passed no entry and has no vote)
+  if (n_reads == 0) return LVA_OK;
+  LsStream st;
+  if (const int so = ls_open(device, &st)) return so;
+  const size_t n = (size_t)n_reads, no = (size_t)num_oligos, pb = n * (size_t)bytes_per_oligo, ob = no * (size_t)bytes_per_oligo;
+  Arena arena;
+  const auto d_index = arena.add<int32_t>(n), d_order = arena.add<int32_t>(n);
+  const auto d_pay = arena.add<uint8_t>(pb);
+  const auto d_bucket = arena.add<int32_t>(no + 1);
+  const auto d_present = arena.add<uint8_t>(no), d_out = arena.add<uint8_t>(ob);
+  const auto d_votes = arena.add<int32_t>(no);
+  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
+  StreamDrain drain(st.s);
+  HIP_TRY(hipMemcpyAsync(arena.ptr(d_index), index, 4 * n, hipMemcpyHostToDevice, st.s));
+  HIP_TRY(hipMemcpyAsync(arena.ptr(d_pay), payload, pb, hipMemcpyHostToDevice, st.s));
+  const int e = launch_ls_consensus(arena.ptr(d_index), arena.ptr(d_pay), n_reads, bytes_per_oligo, num_oligos, first_only ? 1 : 0,
+                                    arena.ptr(d_bucket), arena.ptr(d_order), arena.ptr(d_present), arena.ptr(d_out),
+                                    arena.ptr(d_votes), st.s);
+  if (e) return launch_status(e);
+  HIP_TRY(hipMemcpyAsync(out_present, arena.ptr(d_present), no, hipMemcpyDeviceToHost, st.s));
+  HIP_TRY(hipMemcpyAsync(out_payload, arena.ptr(d_out), ob, hipMemcpyDeviceToHost, st.s));
+  HIP_TRY(hipMemcpyAsync(out_votes, arena.ptr(d_votes), 4 * no, hipMemcpyDeviceToHost, st.s));
+  return drain.finish();
+}
+
+int lva_list_stats(int32_t device, const uint8_t* msgs, const int32_t* counts, const uint8_t* truth, int32_t n_reads,
+                   int32_t list_size, uint32_t msg_len, lva_list_stat* out) {
+  static_assert(sizeof(lva_list_stat) == kLsStatFields * sizeof(int32_t), "ls_stats writes the fields of lva_list_stat in order");
+  if (!msgs || !counts || !truth || !out) return LVA_ERR_ARG;
+  if (!ls_shape_ok(n_reads, list_size, msg_len)) return LVA_ERR_ARG;
+  if (n_reads == 0) return LVA_OK;
+  LsStream st;
+  if (const int so = ls_open(device, &st)) return so;
+  const size_t n = (size_t)n_reads, mb = n * (size_t)list_size * msg_len, tb = n * msg_len;
+  Arena arena;
+  const auto d_msgs = arena.add<uint8_t>(mb);
+  const auto d_counts = arena.add<int32_t>(n);
+  const auto d_truth = arena.add<uint8_t>(tb);
+  const auto d_packed = arena.add<uint64_t>(kLsPackWords * n);
+  const auto d_out = arena.add<int32_t>(kLsStatFields * n);
+  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
+  StreamDrain drain(st.s);
+  HIP_TRY(hipMemcpyAsync(arena.ptr(d_msgs), msgs, mb, hipMemcpyHostToDevice, st.s));
+  HIP_TRY(hipMemcpyAsync(arena.ptr(d_counts), counts, 4 * n, hipMemcpyHostToDevice, st.s));
+  HIP_TRY(hipMemcpyAsync(arena.ptr(d_truth), truth, tb, hipMemcpyHostToDevice, st.s));
+  const int e = launch_ls_stats(arena.ptr(d_msgs), arena.ptr(d_counts), arena.ptr(d_truth), n_reads, list_size, msg_len,
+                                arena.ptr(d_packed), arena.ptr(d_out), st.s);
+  if (e) return launch_status(e);
+  HIP_TRY(hipMemcpyAsync(out, arena.ptr(d_out), 4 * kLsStatFields * n, hipMemcpyDeviceToHost, st.s));
+  return drain.finish();
+}
+
+}  // extern "C"
