@@ -17,22 +17,6 @@ ERRORS = {
     -12: "LVA_ERR_UNSUPPORTED", -13: "LVA_ERR_BUSY",
 }
 
-# every symbol include/lva_decoder.h declares
-EXPORTS = [
-    "lva_version", "lva_abi_version", "lva_strerror", "lva_last_hip_error", "lva_code_describe", "lva_code_tables", "lva_band_table",
-    "lva_encode", "lva_algorithmic_bytes", "lva_decoder_create", "lva_decoder_destroy",
-    "lva_decode_batch", "lva_decode_batch_device", "lva_decoder_profile", "lva_decoder_set_launch_events", "lva_device_alloc",
-    "lva_device_free", "lva_device_upload", "lva_device_synchronize",
-    "lva_decode_windows_device", "lva_basecall_batch", "lva_basecall_batch_device", "lva_find_barcode_batch",
-    "lva_locate_payload_batch", "lva_locate_payload_batch_device",
-    "lva_rs_decode", "lva_rs_encode", "lva_rs_last_error",
-    "lva_stream_open", "lva_stream_close", "lva_stream_submit", "lva_stream_poll", "lva_stream_pending",
-    "lva_transpost_batch", "lva_transpost_batch_device", "lva_device_download",
-    "lva_list_filter", "lva_list_consensus", "lva_list_stats",
-    "lva_demux_batch", "lva_demux_batch_device", "lva_demux_bases_batch",
-]
-
-
 class LvaError(RuntimeError):
     def __init__(self, code, detail=""):
         self.code = code
@@ -92,6 +76,60 @@ class ListStat(ctypes.Structure):
                 ("hamming8", ctypes.c_int32), ("hamming16", ctypes.c_int32), ("edit", ctypes.c_int32)]
 
 
+_int, _vp, _cp = ctypes.c_int, ctypes.c_void_p, ctypes.c_char_p
+_i32, _u32, _u64, _u16 = ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint16
+_code = [_i32, _i32, _u32, _i32, _cp, _u32]          # mem_conv, rate, msg_len, rc, sync_marker, sync_period
+_decode_out = [_vp, _vp, _vp, _vp]                   # rc_flags, out_msgs, out_scores, out_counts
+_demux = [_vp, _i32, _i32, _i32, _vp, _vp]           # exps, n_exps, max_dist, min_margin, out, all_out
+
+# The C ABI, once: every function include/lva_decoder.h declares -> (restype, argtypes), in the header's order
+# (tests/test_abi_table_host.py parses the header and holds this table and the structures above to it)
+ABI = {
+    "lva_version": (_cp, []),
+    "lva_abi_version": (_int, []),
+    "lva_strerror": (_cp, [_int]),
+    "lva_last_hip_error": (_cp, []),
+    "lva_code_describe": (_int, _code + [ctypes.POINTER(CodeInfoStruct)]),
+    "lva_code_tables": (_int, _code + [_vp, _vp, _vp, _vp, _vp]),
+    "lva_band_table": (_int, _code + [_u32, _u32, _vp, _vp]),
+    "lva_encode": (_int, [_i32, _i32, _u32, _vp, _i32, _vp]),
+    "lva_algorithmic_bytes": (_int, _code + [_u32, _u32, _u32, ctypes.POINTER(ctypes.c_double)]),
+    "lva_decoder_create": (_int, [ctypes.POINTER(Config), ctypes.POINTER(_vp)]),
+    "lva_decoder_destroy": (None, [_vp]),
+    "lva_decode_batch": (_int, [_vp, _vp, _vp, _i32] + _decode_out),
+    "lva_decode_batch_device": (_int, [_vp, _vp, _vp, _i32] + _decode_out),
+    "lva_decode_windows_device": (_int, [_vp, _vp, _vp, _vp, _i32] + _decode_out),
+    "lva_decoder_profile": (_int, [_vp, ctypes.POINTER(Profile)]),
+    "lva_decoder_set_launch_events": (_int, [_vp, _i32]),
+    "lva_stream_open": (_int, [_vp, _i32, ctypes.POINTER(_vp)]),
+    "lva_stream_close": (_int, [_vp]),
+    "lva_stream_submit": (_int, [_vp, _vp, ctypes.c_int64, _i32, _u64]),
+    "lva_stream_poll": (_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, ctypes.POINTER(_i32)]),
+    "lva_stream_pending": (_int, [_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
+    "lva_device_alloc": (_int, [_vp, _u64, ctypes.POINTER(_vp)]),
+    "lva_device_free": (_int, [_vp, _vp]),
+    "lva_device_upload": (_int, [_vp, _vp, _vp, _u64]),
+    "lva_device_synchronize": (_int, [_vp]),
+    "lva_device_download": (_int, [_vp, _vp, _vp, _u64]),
+    "lva_transpost_batch": (_int, [_vp, _vp, _vp, _i32, _vp]),
+    "lva_transpost_batch_device": (_int, [_vp, _vp, _vp, _i32, _vp]),
+    "lva_basecall_batch": (_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "lva_basecall_batch_device": (_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "lva_find_barcode_batch": (_int, [_vp, _vp, _vp, _vp, _i32, _cp, _cp, _vp]),
+    "lva_locate_payload_batch": (_int, [_vp, _vp, _vp, _i32, _cp, _cp, _u32, _vp]),
+    "lva_locate_payload_batch_device": (_int, [_vp, _vp, _vp, _i32, _cp, _cp, _u32, _vp]),
+    "lva_demux_batch": (_int, [_vp, _vp, _vp, _i32] + _demux),
+    "lva_demux_batch_device": (_int, [_vp, _vp, _vp, _i32] + _demux),
+    "lva_demux_bases_batch": (_int, [_vp, _vp, _vp, _vp, _i32] + _demux),
+    "lva_rs_decode": (_int, [_i32, _vp, _i32, _i32, _i32, _vp, _i32, _u16, _u16, _vp, _vp]),
+    "lva_rs_encode": (_int, [_i32, _vp, _i32, _i32, _i32, _u16, _vp]),
+    "lva_rs_last_error": (_cp, []),
+    "lva_list_filter": (_int, [_i32, _vp, _vp, _i32, _i32, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "lva_list_consensus": (_int, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "lva_list_stats": (_int, [_i32, _vp, _vp, _vp, _i32, _i32, _u32, _vp]),
+}
+EXPORTS = list(ABI)
+
 _lib = None
 
 
@@ -115,69 +153,23 @@ def load_library():
         raise ImportError("%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "or `make -C nanopore_dna_storage_amd/csrc`" % path)
     L = ctypes.CDLL(path)
-    vp, i32, u32, u64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64
-    cp = ctypes.c_char_p
-    L.lva_version.restype = cp
     if not hasattr(L, "lva_abi_version"):            # a library built before the ABI carried a version (round 4 and earlier)
         raise ImportError("%s has no lva_abi_version (ABI version < 5), this package was written for %d: rebuild it" % (path, ABI_VERSION))
     L.lva_abi_version.restype = ctypes.c_int
     if L.lva_abi_version() != ABI_VERSION:
         raise ImportError("%s has ABI version %d, this package was written for %d (struct layouts of include/lva_decoder.h): rebuild it"
                           % (path, L.lva_abi_version(), ABI_VERSION))
-    L.lva_strerror.restype = cp
-    L.lva_strerror.argtypes = [ctypes.c_int]
-    L.lva_last_hip_error.restype = cp
-    L.lva_code_describe.argtypes = [i32, i32, u32, i32, cp, u32, ctypes.POINTER(CodeInfoStruct)]
-    L.lva_code_tables.argtypes = [i32, i32, u32, i32, cp, u32, vp, vp, vp, vp, vp]
-    L.lva_band_table.argtypes = [i32, i32, u32, i32, cp, u32, u32, u32, vp, vp]
-    L.lva_encode.argtypes = [i32, i32, u32, vp, i32, vp]
-    L.lva_algorithmic_bytes.argtypes = [i32, i32, u32, i32, cp, u32, u32, u32, u32, ctypes.POINTER(ctypes.c_double)]
-    L.lva_decoder_create.argtypes = [ctypes.POINTER(Config), ctypes.POINTER(vp)]
-    L.lva_decoder_destroy.argtypes = [vp]
-    L.lva_decoder_destroy.restype = None
-    L.lva_decode_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
-    L.lva_decode_batch_device.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
-    L.lva_decoder_profile.argtypes = [vp, ctypes.POINTER(Profile)]
-    L.lva_decoder_set_launch_events.argtypes = [vp, i32]
-    L.lva_device_alloc.argtypes = [vp, u64, ctypes.POINTER(vp)]
-    L.lva_device_free.argtypes = [vp, vp]
-    L.lva_device_upload.argtypes = [vp, vp, vp, u64]
-    L.lva_device_synchronize.argtypes = [vp]
-    L.lva_decode_windows_device.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp, vp]
-    L.lva_basecall_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp]
-    L.lva_basecall_batch_device.argtypes = [vp, vp, vp, i32, vp, vp, vp]
-    L.lva_find_barcode_batch.argtypes = [vp, vp, vp, vp, i32, cp, cp, vp]
-    L.lva_locate_payload_batch.argtypes = [vp, vp, vp, i32, cp, cp, u32, vp]
-    L.lva_locate_payload_batch_device.argtypes = [vp, vp, vp, i32, cp, cp, u32, vp]
-    u16 = ctypes.c_uint16
-    L.lva_rs_decode.argtypes = [i32, vp, i32, i32, i32, vp, i32, u16, u16, vp, vp]
-    L.lva_rs_encode.argtypes = [i32, vp, i32, i32, i32, u16, vp]
-    L.lva_rs_last_error.restype = cp
-    if not hasattr(L, "lva_stream_open"):            # additive entry points: the ABI version did not change with them
-        raise ImportError("%s has no decode stream (lva_stream_open): rebuild it" % path)
-    i64 = ctypes.c_int64
-    L.lva_stream_open.argtypes = [vp, i32, ctypes.POINTER(vp)]
-    L.lva_stream_close.argtypes = [vp]
-    L.lva_stream_submit.argtypes = [vp, vp, i64, i32, u64]
-    L.lva_stream_poll.argtypes = [vp, i32, i32, vp, vp, vp, vp, ctypes.POINTER(i32)]
-    L.lva_stream_pending.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]
-    for name in ("lva_transpost_batch", "lva_transpost_batch_device", "lva_device_download"):
-        if not hasattr(L, name):                     # additive as the stream was: same ABI version
-            raise ImportError("%s has no transition posteriors (%s): rebuild it" % (path, name))
-    L.lva_transpost_batch.argtypes = [vp, vp, vp, i32, vp]
-    L.lva_transpost_batch_device.argtypes = [vp, vp, vp, i32, vp]
-    L.lva_device_download.argtypes = [vp, vp, vp, u64]
-    for name in ("lva_list_filter", "lva_list_consensus", "lva_list_stats"):
-        if not hasattr(L, name):                     # additive again: same ABI version
-            raise ImportError("%s has no list consumers (%s): rebuild it" % (path, name))
-    L.lva_list_filter.argtypes = [i32, vp, vp, i32, i32, u32, i32, i32, i32, i32, vp, vp, vp]
-    L.lva_list_consensus.argtypes = [i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    L.lva_list_stats.argtypes = [i32, vp, vp, vp, i32, i32, u32, vp]
-    for name in ("lva_demux_batch", "lva_demux_batch_device", "lva_demux_bases_batch"):
-        if not hasattr(L, name):                     # additive again: same ABI version
-            raise ImportError("%s has no demultiplexing (%s): rebuild it" % (path, name))
-    L.lva_demux_batch.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp]
-    L.lva_demux_batch_device.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp]
-    L.lva_demux_bases_batch.argtypes = [vp, vp, vp, vp, i32, vp, i32, i32, i32, vp, vp]
+    for name, (restype, argtypes) in ABI.items():    # entry points were added without a new ABI version: an older build lacks some
+        if not hasattr(L, name):
+            raise ImportError("%s has no %s: rebuild it" % (path, name))
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
+
+
+def check(status, detail="lva_last_hip_error"):
+    """The one place a non-zero status of the library becomes an LvaError.  detail: the entry point that holds the text of
+    what went wrong (lva_rs_last_error for the outer code), None for the host-only calls that leave none."""
+    if status != 0:
+        raise LvaError(status, getattr(load_library(), detail)().decode() if detail else "")

@@ -5,18 +5,24 @@ Mirrors the reference's operator surface for this path:
   * `Decoder.decode`  <->  `viterbi_nanopore.out -m decode` per read (:226-254), batched.
 """
 import ctypes
+from contextlib import contextmanager
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import _lib
-from ._lib import LvaError, load_library
+from ._lib import LvaError, check, load_library
 
 _BASES = np.frombuffer(b"ACGT", dtype=np.uint8)
 
 
 def _sm(sync_marker):
     return sync_marker.encode() if sync_marker else None
+
+
+def _dist(d):
+    """INT32_MAX of the C ABI = the reference's np.inf: no such distance"""
+    return float("inf") if d == 0x7FFFFFFF else d
 
 
 @dataclass
@@ -38,9 +44,7 @@ def code_info(mem_conv, rate, msg_len, rc=False, sync_marker="", sync_period=0):
     """set_conv_params (:264-415): raises LvaError for parameters the reference rejects."""
     L = load_library()
     s = _lib.CodeInfoStruct()
-    st = L.lva_code_describe(mem_conv, rate, msg_len, int(bool(rc)), _sm(sync_marker), sync_period, ctypes.byref(s))
-    if st != 0:
-        raise LvaError(st)
+    check(L.lva_code_describe(mem_conv, rate, msg_len, int(bool(rc)), _sm(sync_marker), sync_period, ctypes.byref(s)), detail=None)
     return CodeInfo(mem_conv, rate, msg_len, s.nstate_pos, s.nstate_conv, s.oligo_len, s.msg_words,
                     s.initial_state, s.final_state, (s.g0, s.g1), tuple(s.pattern[:s.pattern_len]))
 
@@ -54,11 +58,9 @@ def code_tables(mem_conv, rate, msg_len, rc=False, sync_marker="", sync_period=0
     vmask = np.zeros(info.nstate_pos, np.uint32)
     vval = np.zeros(info.nstate_pos, np.uint32)
     predtab = np.zeros((4, info.nstate_conv), np.uint16)
-    st = L.lva_code_tables(mem_conv, rate, msg_len, int(bool(rc)), _sm(sync_marker), sync_period,
-                           pos2msg.ctypes.data, ptype.ctypes.data, vmask.ctypes.data, vval.ctypes.data,
-                           predtab.ctypes.data)
-    if st != 0:
-        raise LvaError(st)
+    check(L.lva_code_tables(mem_conv, rate, msg_len, int(bool(rc)), _sm(sync_marker), sync_period,
+                            pos2msg.ctypes.data, ptype.ctypes.data, vmask.ctypes.data, vval.ctypes.data,
+                            predtab.ctypes.data), detail=None)
     return dict(pos2msg=pos2msg, ptype=ptype, vmask=vmask, vval=vval, predtab=predtab)
 
 
@@ -69,10 +71,8 @@ def band_table(mem_conv, rate, msg_len, nblk, max_deviation=None, rc=False, sync
     ref = np.zeros((nblk, 2), np.uint32)
     work = np.zeros((nblk, 2), np.uint32)
     md = 0xFFFFFFFF if max_deviation is None else int(max_deviation)
-    st = L.lva_band_table(mem_conv, rate, msg_len, int(bool(rc)), _sm(sync_marker), sync_period, int(nblk), md,
-                          ref.ctypes.data, work.ctypes.data)
-    if st != 0:
-        raise LvaError(st)
+    check(L.lva_band_table(mem_conv, rate, msg_len, int(bool(rc)), _sm(sync_marker), sync_period, int(nblk), md,
+                           ref.ctypes.data, work.ctypes.data), detail=None)
     return ref.astype(np.int64), work.astype(np.int64)
 
 
@@ -86,9 +86,7 @@ def encode(mem_conv, rate, msg_len, msgs):
         raise LvaError(-10, "Message length does not match msg_len parameter.")   # :219-222
     info = code_info(mem_conv, rate, msg_len)
     out = np.zeros((msgs.shape[0], info.oligo_len), np.uint8)
-    st = load_library().lva_encode(mem_conv, rate, msg_len, msgs.ctypes.data, msgs.shape[0], out.ctypes.data)
-    if st != 0:
-        raise LvaError(st)
+    check(load_library().lva_encode(mem_conv, rate, msg_len, msgs.ctypes.data, msgs.shape[0], out.ctypes.data), detail=None)
     return out[0] if single else out
 
 
@@ -105,10 +103,8 @@ def algorithmic_bytes(mem_conv, rate, msg_len, nblk, list_size, max_deviation=No
     """sum_t [2 R(t) L (4+4W) + 160] for one read of nblk blocks."""
     out = ctypes.c_double(0)
     md = _lib.MAX_DEVIATION_DEFAULT if max_deviation is None else max_deviation
-    st = load_library().lva_algorithmic_bytes(mem_conv, rate, msg_len, int(bool(rc)), _sm(sync_marker), sync_period,
-                                              nblk, list_size, md, ctypes.byref(out))
-    if st != 0:
-        raise LvaError(st)
+    check(load_library().lva_algorithmic_bytes(mem_conv, rate, msg_len, int(bool(rc)), _sm(sync_marker), sync_period,
+                                               nblk, list_size, md, ctypes.byref(out)), detail=None)
     return out.value
 
 
@@ -129,9 +125,7 @@ class Decoder:
                           _lib.MAX_DEVIATION_DEFAULT if max_deviation is None else max_deviation,
                           self._sync, sync_period, device, max_slots, kernel, mem_budget_bytes)
         h = ctypes.c_void_p()
-        st = self._L.lva_decoder_create(ctypes.byref(cfg), ctypes.byref(h))
-        if st != 0:
-            raise LvaError(st, self._L.lva_last_hip_error().decode())
+        check(self._L.lva_decoder_create(ctypes.byref(cfg), ctypes.byref(h)))
         self._h = h
         self.mem_conv, self.rate, self.msg_len, self.list_size = mem_conv, rate, msg_len, list_size
         self.device = device
@@ -149,6 +143,8 @@ class Decoder:
 
     def __exit__(self, *a):
         self.close()
+
+    _check = staticmethod(check)       # a status of the library: LvaError with lva_last_hip_error's text unless it is 0
 
     @staticmethod
     def _pack(posts):
@@ -182,18 +178,20 @@ class Decoder:
         back to back), `off` int64 [n+1] block offsets.  The host->device copy happens inside the call."""
         return self._unpack(len(off) - 1, *self._decode_packed_dense(flat, off, rc))
 
-    def _decode_packed_dense(self, flat, off, rc=None):
-        """decode_packed's outputs as the C ABI fills them: msgs uint8 [n, list_size, msg_len], scores, counts"""
-        n = len(off) - 1
-        assert flat.dtype == np.float32 and flat.flags.c_contiguous and off.dtype == np.int64
+    def _decode_call(self, fn, n, rc, *where):
+        """The one decode call: `where` is what the entry point takes between the decoder and n_reads (the buffer and its row
+        offsets, or the buffer and its windows) -> the outputs as the C ABI fills them: msgs uint8 [n, list_size, msg_len],
+        scores float32 [n, list_size], counts int32 [n]"""
         rcf = None if rc is None else np.ascontiguousarray(rc, dtype=np.uint8)
         msgs, scores, counts = self._outputs(n)
-        st = self._L.lva_decode_batch(self._h, flat.ctypes.data, off.ctypes.data, n,
-                                      None if rcf is None else rcf.ctypes.data,
-                                      msgs.ctypes.data, scores.ctypes.data, counts.ctypes.data)
-        if st != 0:
-            raise LvaError(st, self._L.lva_last_hip_error().decode())
+        self._check(fn(self._h, *where, n, None if rcf is None else rcf.ctypes.data,
+                       msgs.ctypes.data, scores.ctypes.data, counts.ctypes.data))
         return msgs, scores, counts
+
+    def _decode_packed_dense(self, flat, off, rc=None):
+        """decode_packed's outputs as the C ABI fills them: msgs uint8 [n, list_size, msg_len], scores, counts"""
+        assert flat.dtype == np.float32 and flat.flags.c_contiguous and off.dtype == np.int64
+        return self._decode_call(self._L.lva_decode_batch, len(off) - 1, rc, flat.ctypes.data, off.ctypes.data)
 
     def decode_payloads(self, posts, rc, bytes_per_oligo, num_oligos, pad=False):
         """decode() followed by the CRC-8 / index filter (helper.decode_list_CRC_index, helper.py:371-388) on the arrays
@@ -208,81 +206,79 @@ class Decoder:
     # --- inputs resident in HBM (bench.py) ---------------------------------------------------
     def upload(self, posts):
         flat, off = self._pack(posts)
-        p = ctypes.c_void_p()
-        st = self._L.lva_device_alloc(self._h, flat.nbytes, ctypes.byref(p))
-        if st != 0:
-            raise LvaError(st, self._L.lva_last_hip_error().decode())
-        st = self._L.lva_device_upload(self._h, p, flat.ctypes.data, flat.nbytes)
-        if st != 0:
-            raise LvaError(st, self._L.lva_last_hip_error().decode())
+        p = self.alloc(flat.nbytes)
+        self._check(self._L.lva_device_upload(self._h, p, flat.ctypes.data, flat.nbytes))
         return p, off
 
     def free(self, dev_ptr):
         self._L.lva_device_free(self._h, dev_ptr)
 
+    @contextmanager
+    def resident(self, data, offsets=None):
+        """A buffer in HBM for the length of a `with` block, freed on every way out of it -> (device pointer, offsets).
+        data: a list of float32 [nblk_i, 40] matrices, packed and uploaded as upload() does; or with `offsets` (int64 [n + 1])
+        one array that holds them back to back already; or a number of bytes, left as allocated (alloc())."""
+        flat, off = None, offsets
+        if not isinstance(data, (int, np.integer)):
+            flat, off = self._pack(data) if offsets is None else (
+                np.ascontiguousarray(data, dtype=np.float32).reshape(-1, 40), np.ascontiguousarray(offsets, dtype=np.int64))
+        dev = self.alloc(data if flat is None else flat.nbytes)
+        try:
+            if flat is not None:
+                self._check(self._L.lva_device_upload(self._h, dev, flat.ctypes.data, flat.nbytes))
+            yield dev, off
+        finally:
+            self.free(dev)
+
     def decode_resident(self, dev_ptr, off, rc=None):
         n = len(off) - 1
-        rcf = None if rc is None else np.ascontiguousarray(rc, dtype=np.uint8)
-        msgs, scores, counts = self._outputs(n)
-        st = self._L.lva_decode_batch_device(self._h, dev_ptr, off.ctypes.data, n,
-                                             None if rcf is None else rcf.ctypes.data,
-                                             msgs.ctypes.data, scores.ctypes.data, counts.ctypes.data)
-        if st != 0:
-            raise LvaError(st, self._L.lva_last_hip_error().decode())
-        return self._unpack(n, msgs, scores, counts)
-
-    def _check(self, st):
-        if st != 0:
-            raise LvaError(st, self._L.lva_last_hip_error().decode())
+        return self._unpack(n, *self._decode_call(self._L.lva_decode_batch_device, n, rc, dev_ptr, off.ctypes.data))
 
     def decode_windows_resident(self, dev_ptr, first_block, n_blocks, rc=None):
         """decode windows [first_block[i], first_block[i] + n_blocks[i]) of a resident posterior buffer in place
         (helper.truncate_post_file + the decode call of generate_decoded_lists.py:80-89, without the copy)"""
         fb = np.ascontiguousarray(first_block, dtype=np.int64)
         nb = np.ascontiguousarray(n_blocks, dtype=np.int64)
-        n = len(fb)
-        rcf = None if rc is None else np.ascontiguousarray(rc, dtype=np.uint8)
-        msgs, scores, counts = self._outputs(n)
-        self._check(self._L.lva_decode_windows_device(self._h, dev_ptr, fb.ctypes.data, nb.ctypes.data, n,
-                                                      None if rcf is None else rcf.ctypes.data,
-                                                      msgs.ctypes.data, scores.ctypes.data, counts.ctypes.data))
-        return self._unpack(n, msgs, scores, counts)
+        return self._unpack(len(fb), *self._decode_call(self._L.lva_decode_windows_device, len(fb), rc, dev_ptr,
+                                                        fb.ctypes.data, nb.ctypes.data))
+
+    def decode_located(self, dev_ptr, off, loc, subset=None):
+        """The windows that were found, decoded where they are: `loc` holds one dict per read of the resident buffer, as
+        locate_payload or demux give them (ok, start_pos, end_pos, rc are read); subset: the read indices to consider
+        (default: all).  One decode_windows_resident call for the reads whose `ok` is set, none when there is no such read.
+        -> [(loc[i], decode result | None)] for every read; None: not found, or not in the subset"""
+        good = [i for i in (range(len(loc)) if subset is None else subset) if loc[i]["ok"]]
+        out = [(lc, None) for lc in loc]
+        if good:
+            dec = self.decode_windows_resident(dev_ptr, [int(off[i]) + loc[i]["start_pos"] for i in good],
+                                               [loc[i]["end_pos"] - loc[i]["start_pos"] + 1 for i in good],
+                                               rc=[loc[i]["rc"] for i in good])
+            for i, r in zip(good, dec):
+                out[i] = (loc[i], r)
+        return out
 
     # --- SURVEY 8(f) row N3: basecall of the posterior matrix + barcode localisation ------------
-    def _basecall_out(self, off, bases, trans, nb):
-        return [(bases[off[i]:off[i] + nb[i]].tobytes().decode("ascii"), trans[off[i]:off[i] + nb[i]].astype(np.int64))
-                for i in range(len(nb))]
-
-    def basecall(self, posts):
-        """flappie's basecall of each posterior matrix (flappie.c:273-285): [(base string, trans positions)]"""
-        n = len(posts)
-        flat, off = self._pack(posts)
-        T = max(int(off[-1]), 1)
-        bases, trans, nb = np.zeros(T, np.uint8), np.zeros(T, np.uint32), np.zeros(max(n, 1), np.int32)
-        self._check(self._L.lva_basecall_batch(self._h, flat.ctypes.data, off.ctypes.data, n, bases.ctypes.data,
-                                               trans.ctypes.data, nb.ctypes.data))
-        return self._basecall_out(off, bases, trans, nb[:n])
-
-    def basecall_resident(self, dev_ptr, off):
+    def _basecall(self, fn, src, off):
         n = len(off) - 1
         T = max(int(off[-1]), 1)
         bases, trans, nb = np.zeros(T, np.uint8), np.zeros(T, np.uint32), np.zeros(max(n, 1), np.int32)
-        self._check(self._L.lva_basecall_batch_device(self._h, dev_ptr, off.ctypes.data, n, bases.ctypes.data,
-                                                      trans.ctypes.data, nb.ctypes.data))
-        return self._basecall_out(off, bases, trans, nb[:n])
+        self._check(fn(self._h, src, off.ctypes.data, n, bases.ctypes.data, trans.ctypes.data, nb.ctypes.data))
+        return [(bases[off[i]:off[i] + nb[i]].tobytes().decode("ascii"), trans[off[i]:off[i] + nb[i]].astype(np.int64))
+                for i in range(n)]
+
+    def basecall(self, posts):
+        """flappie's basecall of each posterior matrix (flappie.c:273-285): [(base string, trans positions)]"""
+        flat, off = self._pack(posts)
+        return self._basecall(self._L.lva_basecall_batch, flat.ctypes.data, off)
+
+    def basecall_resident(self, dev_ptr, off):
+        return self._basecall(self._L.lva_basecall_batch_device, dev_ptr, off)
 
     @staticmethod
-    def _payload_out(res, n):
-        inf = float("inf")
-        big = 0x7FFFFFFF
-        return [dict(ok=bool(r.ok), start_pos=r.start_pos, end_pos=r.end_pos, rc=bool(r.rc),
-                     dist_start=inf if r.dist_start == big else r.dist_start,
-                     dist_end=inf if r.dist_end == big else r.dist_end) for r in res[:n]]
-
-    def find_barcode(self, basecalls, trans_lists, start_barcode, end_barcode):
-        """helper.find_barcode_pos_in_post (helper.py:157-210) for a batch of (basecall, trans list) pairs"""
-        n = len(basecalls)
-        off = np.zeros(n + 1, np.int64)
+    def _pack_bases(basecalls, trans_lists):
+        """(basecall, trans list) pairs in the C ABI's form -> (bases uint8, trans uint32, base offsets int64 [n + 1]); of a
+        trans list the first len(basecall) entries count; an empty batch leaves one placeholder element in each array"""
+        off = np.zeros(len(basecalls) + 1, np.int64)
         off[1:] = np.cumsum([len(b) for b in basecalls])
         for b, t in zip(basecalls, trans_lists):
             if len(t) < len(b):
@@ -290,45 +286,54 @@ class Decoder:
         bases = np.frombuffer("".join(basecalls).encode("ascii") or b"\0", dtype=np.uint8).copy()
         trans = np.concatenate([np.asarray(t, dtype=np.uint32)[:len(b)] for b, t in zip(basecalls, trans_lists)]
                                + [np.zeros(1, np.uint32)])
+        return bases, trans, off
+
+    @staticmethod
+    def _payload_out(res, n):
+        return [dict(ok=bool(r.ok), start_pos=r.start_pos, end_pos=r.end_pos, rc=bool(r.rc),
+                     dist_start=_dist(r.dist_start), dist_end=_dist(r.dist_end)) for r in res[:n]]
+
+    def find_barcode(self, basecalls, trans_lists, start_barcode, end_barcode):
+        """helper.find_barcode_pos_in_post (helper.py:157-210) for a batch of (basecall, trans list) pairs"""
+        n = len(basecalls)
+        bases, trans, off = self._pack_bases(basecalls, trans_lists)
         res = (_lib.PayloadPos * max(n, 1))()
         self._check(self._L.lva_find_barcode_batch(self._h, bases.ctypes.data, trans.ctypes.data, off.ctypes.data, n,
                                                    start_barcode.encode(), end_barcode.encode(), res))
         return self._payload_out(res, n)
 
+    def _locate(self, fn, src, off, start_barcode, end_barcode):
+        n = len(off) - 1
+        res = (_lib.PayloadPos * max(n, 1))()
+        self._check(fn(self._h, src, off.ctypes.data, n, start_barcode.encode(), end_barcode.encode(),
+                       self.mem_conv + self.msg_len + 1, res))
+        return self._payload_out(res, n)
+
     def locate_payload(self, posts, start_barcode, end_barcode):
         """generate_decoded_lists.py:68-79 per read: basecall, barcode search in both orientations, choice.
         -> [dict(ok, start_pos, end_pos, rc, dist_start, dist_end)]"""
-        n = len(posts)
         flat, off = self._pack(posts)
-        res = (_lib.PayloadPos * max(n, 1))()
-        self._check(self._L.lva_locate_payload_batch(self._h, flat.ctypes.data, off.ctypes.data, n, start_barcode.encode(),
-                                                     end_barcode.encode(), self.mem_conv + self.msg_len + 1, res))
-        return self._payload_out(res, n)
+        return self._locate(self._L.lva_locate_payload_batch, flat.ctypes.data, off, start_barcode, end_barcode)
 
     def locate_payload_resident(self, dev_ptr, off, start_barcode, end_barcode):
-        n = len(off) - 1
-        res = (_lib.PayloadPos * max(n, 1))()
-        self._check(self._L.lva_locate_payload_batch_device(self._h, dev_ptr, off.ctypes.data, n, start_barcode.encode(),
-                                                            end_barcode.encode(), self.mem_conv + self.msg_len + 1, res))
-        return self._payload_out(res, n)
+        return self._locate(self._L.lva_locate_payload_batch_device, dev_ptr, off, start_barcode, end_barcode)
 
     # --- DESIGN.md row N3': demultiplexing a pooled run ------------------------------------------
-    @staticmethod
-    def _demux_args(experiments, max_dist, min_margin):
+    def _demux(self, fn, n, where, experiments, max_dist, min_margin, all):
+        """the one demux call: `where` is what the entry point takes between the decoder and n_reads"""
         from .helper import experiment_barcodes
         exps = [experiment_barcodes(e) for e in experiments]
-        arr = (_lib.ExperimentBarcodes * max(len(exps), 1))()
+        k = len(exps)
+        arr = (_lib.ExperimentBarcodes * max(k, 1))()
         for a, (sb, eb, min_len) in zip(arr, exps):
             a.start_barcode, a.end_barcode, a.min_len = sb.encode(), eb.encode(), min_len
-        return arr, len(exps), -1 if max_dist is None or max_dist < 0 else int(max_dist), int(min_margin)
-
-    def _demux_out(self, res, table, n, k, all):
-        inf, big = float("inf"), 0x7FFFFFFF
-        out = []
-        for r, d in zip(res[:n], self._payload_out([r.pos for r in res[:n]], n)):
-            d.update(experiment=r.experiment, reason=r.reason, runner_up=r.runner_up,
-                     runner_up_dist=inf if r.runner_up_dist == big else r.runner_up_dist)
-            out.append(d)
+        res = (_lib.DemuxPos * max(n, 1))()
+        table = (_lib.PayloadPos * max(n * k, 1))() if all else None
+        self._check(fn(self._h, *where, n, arr, k, -1 if max_dist is None or max_dist < 0 else int(max_dist), int(min_margin),
+                       res, table))
+        out = self._payload_out([r.pos for r in res[:n]], n)
+        for r, d in zip(res[:n], out):
+            d.update(experiment=r.experiment, reason=r.reason, runner_up=r.runner_up, runner_up_dist=_dist(r.runner_up_dist))
         if not all:
             return out
         return out, [self._payload_out(table[i * k:(i + 1) * k], k) for i in range(n)]
@@ -339,59 +344,27 @@ class Decoder:
         min_len) tuples or dicts (helper.experiment_barcodes), 1..64 of them.
         -> [dict(locate_payload's fields of the winner, experiment, reason, runner_up, runner_up_dist)];
         all=True: -> (that, [[locate_payload dict per experiment] per read])."""
-        n = len(posts)
         flat, off = self._pack(posts)
-        arr, k, md, mm = self._demux_args(experiments, max_dist, min_margin)
-        res = (_lib.DemuxPos * max(n, 1))()
-        table = (_lib.PayloadPos * max(n * k, 1))() if all else None
-        self._check(self._L.lva_demux_batch(self._h, flat.ctypes.data, off.ctypes.data, n, arr, k, md, mm, res, table))
-        return self._demux_out(res, table, n, k, all)
+        return self._demux(self._L.lva_demux_batch, len(posts), (flat.ctypes.data, off.ctypes.data),
+                           experiments, max_dist, min_margin, all)
 
     def demux_resident(self, dev_ptr, off, experiments, max_dist=None, min_margin=0, all=False):
         """demux() on a resident posterior buffer (upload(), posteriors_resident())"""
         off = np.ascontiguousarray(off, dtype=np.int64)
-        n = len(off) - 1
-        arr, k, md, mm = self._demux_args(experiments, max_dist, min_margin)
-        res = (_lib.DemuxPos * max(n, 1))()
-        table = (_lib.PayloadPos * max(n * k, 1))() if all else None
-        self._check(self._L.lva_demux_batch_device(self._h, dev_ptr, off.ctypes.data, n, arr, k, md, mm, res, table))
-        return self._demux_out(res, table, n, k, all)
+        return self._demux(self._L.lva_demux_batch_device, len(off) - 1, (dev_ptr, off.ctypes.data),
+                           experiments, max_dist, min_margin, all)
 
     def demux_bases(self, basecalls, trans_lists, experiments, max_dist=None, min_margin=0, all=False):
         """demux() on given (basecall, trans list) pairs, as find_barcode takes them, in both orientations"""
-        n = len(basecalls)
-        off = np.zeros(n + 1, np.int64)
-        off[1:] = np.cumsum([len(b) for b in basecalls])
-        for b, t in zip(basecalls, trans_lists):
-            if len(t) < len(b):
-                raise ValueError("trans list shorter than the basecall")
-        bases = np.frombuffer("".join(basecalls).encode("ascii") or b"\0", dtype=np.uint8).copy()
-        trans = np.concatenate([np.asarray(t, dtype=np.uint32)[:len(b)] for b, t in zip(basecalls, trans_lists)]
-                               + [np.zeros(1, np.uint32)])
-        arr, k, md, mm = self._demux_args(experiments, max_dist, min_margin)
-        res = (_lib.DemuxPos * max(n, 1))()
-        table = (_lib.PayloadPos * max(n * k, 1))() if all else None
-        self._check(self._L.lva_demux_bases_batch(self._h, bases.ctypes.data, trans.ctypes.data, off.ctypes.data, n,
-                                                  arr, k, md, mm, res, table))
-        return self._demux_out(res, table, n, k, all)
+        bases, trans, off = self._pack_bases(basecalls, trans_lists)
+        return self._demux(self._L.lva_demux_bases_batch, len(basecalls), (bases.ctypes.data, trans.ctypes.data, off.ctypes.data),
+                           experiments, max_dist, min_margin, all)
 
     def decode_with_barcodes(self, posts, start_barcode, end_barcode):
         """The real-data chain of generate_decoded_lists.py:68-89 on the device: posteriors are uploaded once,
         payload windows located, then decoded in place.  -> [(locate dict, decode result or None)]"""
-        n = len(posts)
-        dev, off = self.upload(posts)
-        try:
-            loc = self.locate_payload_resident(dev, off, start_barcode, end_barcode)
-            good = [i for i in range(n) if loc[i]["ok"]]
-            dec = self.decode_windows_resident(dev, [off[i] + loc[i]["start_pos"] for i in good],
-                                               [loc[i]["end_pos"] - loc[i]["start_pos"] + 1 for i in good],
-                                               rc=[loc[i]["rc"] for i in good]) if good else []
-        finally:
-            self.free(dev)
-        out = [(loc[i], None) for i in range(n)]
-        for i, r in zip(good, dec):
-            out[i] = (loc[i], r)
-        return out
+        with self.resident(posts) as (dev, off):
+            return self._decode_chain_resident(dev, off, None, start_barcode, end_barcode)
 
     # --- DESIGN.md row N0: transition posteriors from a network's transition scores ---------------
     def posteriors(self, scores):
@@ -421,20 +394,11 @@ class Decoder:
         return [flat[off[i]:off[i + 1]].copy() for i in range(len(off) - 1)]
 
     def _decode_chain_resident(self, dev, off, rc, start_barcode, end_barcode):
-        n = len(off) - 1
         if start_barcode is None and end_barcode is None:
             return self.decode_resident(dev, off, rc)
         if start_barcode is None or end_barcode is None or rc is not None:
             raise ValueError("give both barcodes (the orientation is then found, not passed), or neither")
-        loc = self.locate_payload_resident(dev, off, start_barcode, end_barcode)
-        good = [i for i in range(n) if loc[i]["ok"]]
-        dec = self.decode_windows_resident(dev, [off[i] + loc[i]["start_pos"] for i in good],
-                                           [loc[i]["end_pos"] - loc[i]["start_pos"] + 1 for i in good],
-                                           rc=[loc[i]["rc"] for i in good]) if good else []
-        out = [(loc[i], None) for i in range(n)]
-        for i, r in zip(good, dec):
-            out[i] = (loc[i], r)
-        return out
+        return self.decode_located(dev, off, self.locate_payload_resident(dev, off, start_barcode, end_barcode))
 
     def decode_from_scores(self, scores, rc=None, start_barcode=None, end_barcode=None, offsets=None):
         """scores -> posteriors -> (barcode localisation ->) decoded lists without leaving the device: the scores are
@@ -444,18 +408,10 @@ class Decoder:
         decoder's device with `offsets` (int64 [n + 1] block offsets): its memory is read where it is and not modified --
         the posteriors go to a buffer of the decoder's.  (A process that uses torch and this library initialises torch's
         device first: INTEGRATION.md section 2.)"""
-        if isinstance(scores, (list, tuple)) or isinstance(scores, np.ndarray):
-            if offsets is not None:
-                flat, off = np.ascontiguousarray(scores, dtype=np.float32).reshape(-1, 40), np.ascontiguousarray(offsets, dtype=np.int64)
-                dev = self.alloc(flat.nbytes)
-                self._check(self._L.lva_device_upload(self._h, dev, flat.ctypes.data, flat.nbytes))
-            else:
-                dev, off = self.upload(scores)
-            try:
+        if isinstance(scores, (list, tuple, np.ndarray)):
+            with self.resident(scores, offsets) as (dev, off):
                 self.posteriors_resident(dev, off)
                 return self._decode_chain_resident(dev, off, rc, start_barcode, end_barcode)
-            finally:
-                self.free(dev)
         import torch                              # only here: the package imports without torch
         if not isinstance(scores, torch.Tensor):
             raise TypeError("scores: a list of [nblk, 40] arrays or one torch tensor with offsets")
@@ -469,12 +425,9 @@ class Decoder:
         if int(off[-1]) != scores.shape[0]:
             raise ValueError("offsets end at %d, the tensor has %d blocks" % (int(off[-1]), scores.shape[0]))
         torch.cuda.current_stream(scores.device).synchronize()     # the decoder works on a stream of its own
-        dev = self.alloc(scores.shape[0] * 160)
-        try:
+        with self.resident(scores.shape[0] * 160) as (dev, _):
             self.posteriors_resident(ctypes.c_void_p(scores.data_ptr()), off, out_ptr=dev)
             return self._decode_chain_resident(dev, off, rc, start_barcode, end_barcode)
-        finally:
-            self.free(dev)
 
     # --- decode stream: reads go in one at a time, results come out as they finish -------------
     def stream(self, queue_cap=None):

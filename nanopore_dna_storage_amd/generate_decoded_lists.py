@@ -119,39 +119,29 @@ def decode_score_rows(args, rows, dec, min_len):
     """decode_rows for files of raw transition scores: the chunk is uploaded once and turned into posteriors in place (the
     posteriors of a block depend on the whole read, so windows are cut afterwards); from there on the rows are handled as
     untruncated .post files are -- barcode search + windows for rows without a block range, the given windows otherwise"""
-    results = [BARCODE_FAILURE] * len(rows)
     located = {}
-    dev, off = dec.upload([helper.read_post_file(r[2]) for r in rows])
-    try:
+    # the windows the manifest supplied, in locate_payload's form (ok: the skip rule, :76); None: a row to search
+    loc = [None if r[3] is None else dict(ok=not (r[3] == -1 or r[4] - r[3] + 1 < min_len), start_pos=r[3], end_pos=r[4], rc=r[5])
+           for r in rows]
+    todo = [i for i, lc in enumerate(loc) if lc is None]
+    with dec.resident([helper.read_post_file(r[2]) for r in rows]) as (dev, off):
         dec.posteriors_resident(dev, off)
-        todo = [i for i, r in enumerate(rows) if r[3] is None]
-        win = {}                                               # row -> (first block in the buffer, blocks, rc)
-        if todo:
-            if len(todo) == len(rows):
-                loc = dec.locate_payload_resident(dev, off, args.start_barcode, args.end_barcode)
-            else:                                              # mixed manifest: the rows to search, one read per call
-                loc = []
-                for i in todo:
-                    one = np.array([0, off[i + 1] - off[i]], np.int64)
-                    loc += dec.locate_payload_resident(ctypes.c_void_p(dev.value + int(off[i]) * 160), one,
-                                                       args.start_barcode, args.end_barcode)
-            for i, lc in zip(todo, loc):
-                located[i] = dict(start_pos=int(lc["start_pos"]), end_pos=int(lc["end_pos"]), rc=bool(lc["rc"]))
-                if lc["ok"]:
-                    win[i] = (int(off[i]) + lc["start_pos"], lc["end_pos"] - lc["start_pos"] + 1, lc["rc"])
+        if len(todo) == len(rows):
+            found = dec.locate_payload_resident(dev, off, args.start_barcode, args.end_barcode)
+        else:                                                  # mixed manifest: the rows to search, one read per call
+            found = []
+            for i in todo:
+                one = np.array([0, off[i + 1] - off[i]], np.int64)
+                found += dec.locate_payload_resident(ctypes.c_void_p(dev.value + int(off[i]) * 160), one,
+                                                     args.start_barcode, args.end_barcode)
+        for i, lc in zip(todo, found):
+            loc[i] = lc
+            located[i] = dict(start_pos=int(lc["start_pos"]), end_pos=int(lc["end_pos"]), rc=bool(lc["rc"]))
         for i, r in enumerate(rows):
-            if r[3] is not None and not (r[3] == -1 or r[4] - r[3] + 1 < min_len):
+            if r[3] is not None and loc[i]["ok"]:
                 assert r[3] >= 0 and off[i + 1] - off[i] >= r[4] + 1     # helper.truncate_post
-                win[i] = (int(off[i]) + r[3], r[4] - r[3] + 1, r[5])
-        order = sorted(win)
-        if order:
-            dec_res = dec.decode_windows_resident(dev, [win[i][0] for i in order], [win[i][1] for i in order],
-                                                  rc=[win[i][2] for i in order])
-            for i, res in zip(order, dec_res):
-                results[i] = res
-    finally:
-        dec.free(dev)
-    return results, located
+        chain = dec.decode_located(dev, off, loc)
+    return [BARCODE_FAILURE if res is None else res for _, res in chain], located
 
 
 TMP_PREFIX = ".tmp-"

@@ -15,15 +15,10 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import LvaError, load_library
+from ._lib import check, load_library
 
 STAT_FIELDS = ("top_correct", "list_correct", "hamming", "hamming8", "hamming16", "edit")
 STAT_DTYPE = np.dtype([(k, np.int32) for k in STAT_FIELDS])
-
-
-def _check(st):
-    if st != 0:
-        raise LvaError(st, load_library().lva_last_hip_error().decode())
 
 
 def bits_of(s):
@@ -99,7 +94,7 @@ def filter_lists(msgs, counts, bytes_per_oligo, num_oligos, pad=False, list_size
     index = np.full(n, -1, np.int32)
     rank = np.full(n, -1, np.int32)
     payload = np.zeros((n, bytes_per_oligo), np.uint8)
-    _check(load_library().lva_list_filter(device, msgs.ctypes.data, counts.ctypes.data, n, L, msg_len, use, bytes_per_oligo,
+    check(load_library().lva_list_filter(device, msgs.ctypes.data, counts.ctypes.data, n, L, msg_len, use, bytes_per_oligo,
                                           num_oligos, int(bool(pad)), index.ctypes.data, rank.ctypes.data, payload.ctypes.data))
     return index, rank, payload
 
@@ -113,7 +108,7 @@ def consensus_arrays(index, payload, num_oligos, first_only=False, device=0):
     present = np.zeros(num_oligos, np.uint8)
     out = np.zeros((num_oligos, payload.shape[1]), np.uint8)
     votes = np.zeros(num_oligos, np.int32)
-    _check(load_library().lva_list_consensus(device, index.ctypes.data, payload.ctypes.data, len(index), payload.shape[1], num_oligos,
+    check(load_library().lva_list_consensus(device, index.ctypes.data, payload.ctypes.data, len(index), payload.shape[1], num_oligos,
                                              int(bool(first_only)), present.ctypes.data, out.ctypes.data, votes.ctypes.data))
     return present.astype(bool), out, votes
 
@@ -136,5 +131,5 @@ def list_stats(msgs, counts, truth, device=0):
         raise ValueError("truth must be [n, msg_len]")
     out = np.zeros(n, STAT_DTYPE)
     assert out.itemsize == ctypes.sizeof(_lib.ListStat)
-    _check(load_library().lva_list_stats(device, msgs.ctypes.data, counts.ctypes.data, truth.ctypes.data, n, L, msg_len, out.ctypes.data))
+    check(load_library().lva_list_stats(device, msgs.ctypes.data, counts.ctypes.data, truth.ctypes.data, n, L, msg_len, out.ctypes.data))
     return out

@@ -93,26 +93,20 @@ def decode_pooled(inputs, experiments, device=0, input_kind="post", max_dist=Non
     out = [None] * n
     if n == 0:
         return []
-    with Decoder(*FRONT_CODE, list_size=1, device=device, max_slots=1) as front:
-        dev, off = front.upload(inputs)
-        try:
-            if input_kind == "scores":
-                front.posteriors_resident(dev, off)
-            loc = front.demux_resident(dev, off, experiments, max_dist=max_dist, min_margin=min_margin)
-            out = [(lc, None) for lc in loc]
-            for e, x in enumerate(experiments):
-                mine = [i for i in range(n) if loc[i]["reason"] == 0 and loc[i]["experiment"] == e]
-                if not mine:
-                    continue
-                with Decoder(x["mem_conv"], x["rate_conv"], x["msg_len"], list_size=x["list_size"], max_deviation=max_deviation,
-                             device=device) as dec:
-                    res = dec.decode_windows_resident(dev, [int(off[i]) + loc[i]["start_pos"] for i in mine],
-                                                      [loc[i]["end_pos"] - loc[i]["start_pos"] + 1 for i in mine],
-                                                      rc=[loc[i]["rc"] for i in mine])
-                for i, r in zip(mine, res):
-                    out[i] = (loc[i], r)
-        finally:
-            front.free(dev)
+    with Decoder(*FRONT_CODE, list_size=1, device=device, max_slots=1) as front, front.resident(inputs) as (dev, off):
+        if input_kind == "scores":
+            front.posteriors_resident(dev, off)
+        loc = front.demux_resident(dev, off, experiments, max_dist=max_dist, min_margin=min_margin)
+        out = [(lc, None) for lc in loc]
+        for e, x in enumerate(experiments):
+            mine = [i for i in range(n) if loc[i]["reason"] == 0 and loc[i]["experiment"] == e]
+            if not mine:
+                continue
+            with Decoder(x["mem_conv"], x["rate_conv"], x["msg_len"], list_size=x["list_size"], max_deviation=max_deviation,
+                         device=device) as dec:
+                res = dec.decode_located(dev, off, loc, mine)
+            for i in mine:
+                out[i] = res[i]
     return out
 
 

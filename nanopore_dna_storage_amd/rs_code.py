@@ -20,14 +20,9 @@ reference raises FileNotFoundError there, RSCode_16bit_fileio.py:130-131).
 import numpy as np
 
 from . import helper
-from ._lib import LvaError, load_library
+from ._lib import check, load_library
 
 PAD = 0x3030          # b'0' * 2: rjust(..., b'0') padding (:58, :104), dummy reads (:242) and the fill of a failed column (:123)
-
-
-def _check(st):
-    if st != 0:
-        raise LvaError(st, load_library().lva_rs_last_error().decode())
 
 
 def _columns(reads):
@@ -48,7 +43,7 @@ def MainEncoder(listofreads, redundancy, device=0):
     cols = _columns(listofreads)
     s, n = cols.shape
     out = np.zeros((s, n + redundancy), np.uint16)
-    _check(load_library().lva_rs_encode(device, cols.ctypes.data, s, n, redundancy, PAD, out.ctypes.data))
+    check(load_library().lva_rs_encode(device, cols.ctypes.data, s, n, redundancy, PAD, out.ctypes.data), detail="lva_rs_last_error")
     return _reads(out)
 
 
@@ -70,9 +65,9 @@ def MainDecoder(listofcorruptedreads, redundancy, totalnumreads, device=0, retur
     n_data = totalnumreads - redundancy
     out = np.zeros((spr, n_data), np.uint16)
     ok = np.zeros(spr, np.int32)
-    _check(load_library().lva_rs_decode(device, cols.ctypes.data, spr, totalnumreads, redundancy,
-                                        erasures.ctypes.data if len(erasures) else None, len(erasures), PAD, PAD,
-                                        out.ctypes.data, ok.ctypes.data))
+    check(load_library().lva_rs_decode(device, cols.ctypes.data, spr, totalnumreads, redundancy,
+                                       erasures.ctypes.data if len(erasures) else None, len(erasures), PAD, PAD,
+                                       out.ctypes.data, ok.ctypes.data), detail="lva_rs_last_error")
     dec = _reads(out)
     return (dec, ok.astype(bool)) if return_ok else dec
 
