@@ -52,12 +52,14 @@ typedef struct lva_config {
   uint32_t sync_period;
   int32_t device;           /* HIP device ordinal */
   int32_t max_slots;        /* reads in flight on the device; 0 = choose from free HBM */
-  int32_t kernel;           /* 0 = default (4 where it is the faster one, else 2 where available, else 3, else 1);
-                               1 = exact kernel, one thread per target; 2 = fast kernel + exact fix-up (L = 1, 2, 4, 8:
-                               lva_step_fast / lva_step_acs; any other 2 <= L <= 64: lva_step_big); 3 = exact kernel, one
-                               wavefront per target (2 <= L <= 256: lva_step_wave up to 64 entries, lva_step_wave_wide
-                               above; never the default above 64, which stays 1); 4 = fast kernel with lazy messages (L = 2, 4, 8:
-                               messages materialised every second time step, lva_step_lazy).  Every mode gives the
+  int32_t kernel;           /* 0 = default (4 where it is the faster one, else 2 where available, else 1); 1 = exact kernel,
+                               one thread per target; 2 = fast kernel + exact fix-up (L = 1, 2, 4, 8: lva_step_fast /
+                               lva_step_acs; any other 2 <= L <= 64: lva_step_big); 3 = exact kernel, one wavefront per
+                               target (2 <= L <= 256: lva_step_wave up to 64 entries, lva_step_wave_wide above; never
+                               the default); 4 = fast kernel with lazy messages (L = 2, 4, 8: messages materialised
+                               every second time step, lva_step_lazy).  A mode whose kernels do not serve the list
+                               size is LVA_ERR_UNSUPPORTED, any other value LVA_ERR_ARG; lva_kernel_plan tells what a
+                               configuration resolves to.  Every mode gives the
                                reference's lists bit for bit on every input the reference decodes: targets the fast
                                kernels cannot decide (score ties, non-finite sums, fingerprint collisions) go through a
                                work list to an exact pass, and when that list overflows (tie-dense posteriors: quantised
@@ -106,8 +108,8 @@ typedef struct lva_profile {
 const char *lva_version(void);
 /* LVA_ABI_VERSION of the library that was loaded.  It changes whenever a struct of this header changes size or layout
  * (5: lva_profile gained overflow_steps and working_bytes): a caller built against another value must not pass structs.
- * Entry points added since (lva_stream_*, lva_transpost_*, lva_device_download, lva_list_*, lva_demux_*) change no struct
- * and keep it at 5. */
+ * Entry points added since (lva_stream_*, lva_transpost_*, lva_device_download, lva_list_*, lva_demux_*, lva_kernel_plan)
+ * change no struct and keep it at 5. */
 #define LVA_ABI_VERSION 5
 int lva_abi_version(void);
 const char *lva_strerror(int code);
@@ -145,10 +147,40 @@ int lva_algorithmic_bytes(int32_t mem_conv, int32_t rate, uint32_t msg_len, int3
                           const char *sync_marker, uint32_t sync_period, uint32_t nblk,
                           uint32_t list_size, uint32_t max_deviation, double *out);
 
+/* Which step kernel a configuration runs, and on which trellis layout: what lva_decoder_create decides before it looks at a
+ * device (csrc/lva_plan.h plan_kernels; the table is in DESIGN.md section 4). */
+#define LVA_STEP_EXACT 0      /* lva_step_exact */
+#define LVA_STEP_WAVE 1       /* lva_step_wave */
+#define LVA_STEP_WAVE_WIDE 2  /* lva_step_wave_wide<instance>, instance = ceil(list_size / 64) */
+#define LVA_STEP_ACS 3        /* lva_step_acs */
+#define LVA_STEP_FAST 4       /* lva_step_fast */
+#define LVA_STEP_LAZY 5       /* lva_step_lazy */
+#define LVA_STEP_BIG 6        /* lva_step_big<instance>, instance = 16, 32 or 64 list entries */
+#define LVA_STEP_BIG_REC 7    /* lva_step_big_rec<instance>, instance = 32 or 64 */
+#define LVA_FIXUP_NONE 0
+#define LVA_FIXUP_WAVE 1      /* lva_step_fixup_wave */
+#define LVA_FIXUP_LAZY 2      /* lva_step_fixup_lazy */
+typedef struct lva_kernel_plan_info {
+  int32_t mode;             /* the kernel mode that runs, 1..4: lva_profile.kernel of a decoder of this configuration */
+  int32_t dominant;         /* LVA_STEP_* */
+  int32_t fixup;            /* LVA_FIXUP_*: the exact pass over the dominant kernel's work list */
+  uint32_t lazy, rec, cmp;  /* layout: back-pointer bytes behind every list, record layout, compact lists at one-bit positions */
+  uint32_t ring_positions;  /* trellis positions stored per parity buffer */
+  int32_t instance;         /* template instance of the dominant kernel where it has one (above), else 0 */
+} lva_kernel_plan_info;
+
+/* Host only, opens no device.  Its refusals are lva_decoder_create's first ones, in the same order: LVA_ERR_ARG for a list_size
+ * outside 1..65535, the code's errors, LVA_ERR_MSG_TOO_LONG, LVA_ERR_TOO_MANY_STATES for the state index, LVA_ERR_ARG for a
+ * kernel outside 0..4, LVA_ERR_UNSUPPORTED for a kernel mode that does not serve the list size.  (lva_decoder_create then lays
+ * the trellis out -- LVA_ERR_TOO_MANY_STATES when one parity buffer passes 2^32 words -- and only then looks at the device.)
+ * cfg->device, max_slots and mem_budget_bytes are not looked at. */
+int lva_kernel_plan(const lva_config *cfg, lva_kernel_plan_info *out);
+
 /* --- decoder ------------------------------------------------------------------------------ */
 
 /* Replaces process start-up of `viterbi_nanopore.out -m decode` (main :137-214, set_conv_params,
- * table construction :624-650).  Fails with LVA_ERR_NO_DEVICE when no GPU is usable. */
+ * table construction :624-650).  The configuration is checked first (lva_kernel_plan's errors), then the device:
+ * LVA_ERR_NO_DEVICE when no GPU is usable. */
 int lva_decoder_create(const lva_config *cfg, lva_decoder **out);
 void lva_decoder_destroy(lva_decoder *d);
 

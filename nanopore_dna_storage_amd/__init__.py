@@ -8,4 +8,4 @@ HIP library or a GPU is missing.
 """
 from ._lib import LvaError, library_path, load_library  # noqa: F401
 from .decoder import (CodeInfo, Decoder, algorithmic_bytes, band_table, code_info, code_tables, encode,  # noqa: F401
-                      bases_to_str, str_to_bits)
+                      kernel_plan, bases_to_str, str_to_bits)

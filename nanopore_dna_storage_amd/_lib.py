@@ -57,6 +57,12 @@ class Profile(ctypes.Structure):
                 ("overflow_steps", ctypes.c_uint64), ("working_bytes", ctypes.c_double)]
 
 
+class KernelPlanInfo(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_int32), ("dominant", ctypes.c_int32), ("fixup", ctypes.c_int32),
+                ("lazy", ctypes.c_uint32), ("rec", ctypes.c_uint32), ("cmp", ctypes.c_uint32),
+                ("ring_positions", ctypes.c_uint32), ("instance", ctypes.c_int32)]
+
+
 class PayloadPos(ctypes.Structure):
     _fields_ = [("start_pos", ctypes.c_int32), ("end_pos", ctypes.c_int32), ("dist_start", ctypes.c_int32),
                 ("dist_end", ctypes.c_int32), ("rc", ctypes.c_int32), ("ok", ctypes.c_int32)]
@@ -94,6 +100,7 @@ ABI = {
     "lva_band_table": (_int, _code + [_u32, _u32, _vp, _vp]),
     "lva_encode": (_int, [_i32, _i32, _u32, _vp, _i32, _vp]),
     "lva_algorithmic_bytes": (_int, _code + [_u32, _u32, _u32, ctypes.POINTER(ctypes.c_double)]),
+    "lva_kernel_plan": (_int, [ctypes.POINTER(Config), ctypes.POINTER(KernelPlanInfo)]),
     "lva_decoder_create": (_int, [ctypes.POINTER(Config), ctypes.POINTER(_vp)]),
     "lva_decoder_destroy": (None, [_vp]),
     "lva_decode_batch": (_int, [_vp, _vp, _vp, _i32] + _decode_out),

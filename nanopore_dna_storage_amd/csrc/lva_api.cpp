@@ -15,6 +15,7 @@
 #include <deque>
 #include <limits>
 #include <numeric>
+#include <utility>
 
 #include "lva_host.h"
 #include "lva_kernels.h"
@@ -211,72 +212,87 @@ static int upload_codes(lva_decoder* d) {
   return LVA_OK;
 }
 
+// Positions at which every tile of 64 source conv states feeds at least one valid target conv state, in both orientations:
+// the longest run [full_lo, full_hi].  A target conv state of tile x at position p is  x*Tn + low + leg*(N >> sh)  (low < Tn =
+// 64 >> sh, leg < 2^sh): its middle bits are the tile's, so the tile has a valid target iff those bits agree with the mask.
+static void full_tile_positions(lva_decoder* d) {
+  const Code& c = d->code[0];
+  const uint32_t N = c.nconv;
+  std::vector<uint8_t> full(c.npos, 0);
+  for (uint32_t p = 1; p < c.npos; ++p) {
+    bool ok = N >= 64;
+    for (int o = 0; o < 2 && ok; ++o) {
+      const Code& co = d->code[o];
+      const uint32_t sh = co.ptype[p] == 0 ? 1u : 2u, Tn = 64u >> sh;
+      const uint32_t mid = (N - 1) & ~(Tn - 1) & ~(((1u << sh) - 1u) << ((uint32_t)co.mem_conv - sh));
+      for (uint32_t x = 0; x < N / 64 && ok; ++x) ok = ((x * Tn) & co.vmask[p] & mid) == (co.vval[p] & mid);
+    }
+    full[p] = ok ? 1 : 0;
+  }
+  uint32_t best = 0, run = 0;
+  for (uint32_t p = 1; p < c.npos; ++p) {
+    run = full[p] ? run + 1 : 0;
+    if (run > best) { best = run; d->full_hi = p; d->full_lo = p + 1 - run; }
+  }
+}
+
+// What a configuration decides before its trellis is laid out, in the order its refusals are reported: the codes of both
+// orientations, the limits of the message and the state index, the band half-width, the kernel plan and the ring length.
+static int plan_config(const lva_config* cfg, Code* code, uint32_t* max_dev, Plan* plan, uint32_t* ring) {
+  if (cfg->list_size == 0 || cfg->list_size > 65535) return LVA_ERR_ARG;
+  for (int o = 0; o < 2; ++o) {
+    const int st = build_code(&code[o], cfg->mem_conv, cfg->rate, cfg->msg_len, o, cfg->sync_marker ? cfg->sync_marker : "", cfg->sync_period);
+    if (st != LVA_OK) return st;
+  }
+  const Code& c = code[0];
+  if (c.msg_len > 255 || c.msg_len + (uint32_t)c.mem_conv > 256) return LVA_ERR_MSG_TOO_LONG;
+  if ((uint64_t)c.npos * kCrf * c.nconv >= ((uint64_t)1 << 32)) return LVA_ERR_TOO_MANY_STATES;
+  *max_dev = cfg->max_deviation == LVA_MAX_DEVIATION_DEFAULT ? c.msg_len + (uint32_t)c.mem_conv + 1 : cfg->max_deviation;
+  const int st = plan_kernels(cfg->kernel, cfg->list_size, c.msg_bits(), plan);
+  if (st != LVA_OK) return st;
+  *ring = (uint32_t)std::max<uint64_t>(std::min<uint64_t>(c.npos, 2ull * *max_dev + plan->ring_extra), 1);
+  return LVA_OK;
+}
+
+int lva_kernel_plan(const lva_config* cfg, lva_kernel_plan_info* out) {
+  if (!cfg || !out) return LVA_ERR_ARG;
+  Code code[2];
+  uint32_t max_dev, ring;
+  Plan plan;
+  const int st = plan_config(cfg, code, &max_dev, &plan, &ring);
+  if (st != LVA_OK) return st;
+  out->mode = plan.mode; out->dominant = (int32_t)plan.dominant; out->fixup = (int32_t)plan.fixup;
+  out->lazy = plan.lazy; out->rec = plan.rec; out->cmp = plan.cmp;
+  out->ring_positions = ring; out->instance = plan.inst;
+  return LVA_OK;
+}
+
 int lva_decoder_create(const lva_config* cfg, lva_decoder** out) {
   if (!cfg || !out) return LVA_ERR_ARG;
   *out = nullptr;
-  if (cfg->list_size == 0 || cfg->list_size > 65535) return LVA_ERR_ARG;
+  Code code[2];
+  uint32_t max_dev, ring;
+  Plan plan;
+  {
+    const int st = plan_config(cfg, code, &max_dev, &plan, &ring);
+    if (st != LVA_OK) return st;
+  }
+  const Geometry g = make_geometry(code[0].nconv, cfg->list_size, code[0].msg_bits(), ring, plan.lazy, plan.rec, plan.cmp);
+  if (g.sPar >= ((uint64_t)1 << 32)) return LVA_ERR_TOO_MANY_STATES;
   lva_decoder* d = new (std::nothrow) lva_decoder();
   if (!d) return LVA_ERR_NOMEM;
+  auto fail = [&](int code) { lva_decoder_destroy(d); return code; };
   d->cfg = *cfg;
   d->sync_marker = cfg->sync_marker ? cfg->sync_marker : "";
   d->cfg.sync_marker = nullptr;
-  for (int o = 0; o < 2; ++o) {
-    const int st = build_code(&d->code[o], cfg->mem_conv, cfg->rate, cfg->msg_len, o, d->sync_marker.c_str(),
-                              cfg->sync_period);
-    if (st != LVA_OK) { delete d; return st; }
-  }
+  d->code[0] = std::move(code[0]); d->code[1] = std::move(code[1]);
+  d->max_dev = max_dev; d->plan = plan; d->g = g;
+  d->prof.kernel = plan.mode;
+  full_tile_positions(d);
   const Code& c = d->code[0];
-  if (c.msg_len > 255 || c.msg_len + (uint32_t)c.mem_conv > 256) { delete d; return LVA_ERR_MSG_TOO_LONG; }
-  if ((uint64_t)c.npos * kCrf * c.nconv >= ((uint64_t)1 << 32)) { delete d; return LVA_ERR_TOO_MANY_STATES; }
-  d->max_dev = cfg->max_deviation == LVA_MAX_DEVIATION_DEFAULT ? c.msg_len + (uint32_t)c.mem_conv + 1 : cfg->max_deviation;
-  {
-    // Positions at which every tile of 64 source conv states feeds at least one valid target conv state, in both orientations:
-    // the longest run [full_lo, full_hi].  A target conv state of tile x at position p is  x*Tn + low + leg*(N >> sh)  (low < Tn =
-    // 64 >> sh, leg < 2^sh): its middle bits are the tile's, so the tile has a valid target iff those bits agree with the mask.
-    const uint32_t N = c.nconv;
-    std::vector<uint8_t> full(c.npos, 0);
-    for (uint32_t p = 1; p < c.npos; ++p) {
-      bool ok = N >= 64;
-      for (int o = 0; o < 2 && ok; ++o) {
-        const Code& co = d->code[o];
-        const uint32_t sh = co.ptype[p] == 0 ? 1u : 2u, Tn = 64u >> sh;
-        const uint32_t mid = (N - 1) & ~(Tn - 1) & ~(((1u << sh) - 1u) << ((uint32_t)co.mem_conv - sh));
-        for (uint32_t x = 0; x < N / 64 && ok; ++x) ok = ((x * Tn) & co.vmask[p] & mid) == (co.vval[p] & mid);
-      }
-      full[p] = ok ? 1 : 0;
-    }
-    uint32_t best = 0, run = 0;
-    for (uint32_t p = 1; p < c.npos; ++p) {
-      run = full[p] ? run + 1 : 0;
-      if (run > best) { best = run; d->full_hi = p; d->full_lo = p + 1 - run; }
-    }
-  }
-  // kernel mode 4 ("lazy", list sizes 2, 4, 8): messages are materialised every second time step and carried as one-byte
-  // back-pointers in between; two-hop chains reach one position further below the band, hence one more ring position
-  // Default (kernel 0) for list sizes 2 / 4 / 8 (m = 11 L = 8: +5 % over kernel 2, m = 8: +9 %; m = 14 with four message planes: +8 %
-  // since the anchor instance keeps one entry in flight there).
-  const bool lazy_ok = (cfg->list_size == 2 || cfg->list_size == 4 || cfg->list_size == 8) && c.nconv >= 64;
-  if (cfg->kernel == 4 && !lazy_ok) { delete d; return LVA_ERR_UNSUPPORTED; }
-  const bool lazy = cfg->kernel == 4 || (cfg->kernel == 0 && lazy_ok);
-  const uint64_t ring = std::min<uint64_t>(c.npos, 2ull * d->max_dev + (lazy ? 2 : 1));
-  // the big-list kernel (kernel mode 2 at list sizes without a small-list instance) keeps its lists in the record layout
-  // where the message has three planes and L is a multiple of 4 (Geometry::rec)
-  const bool small = cfg->list_size == 1 || cfg->list_size == 2 || cfg->list_size == 4 || cfg->list_size == 8;
-  const bool big = !lazy && !small && cfg->list_size <= 64 && (cfg->kernel == 0 || cfg->kernel == 2) && c.nconv >= 64;
-  // compact lists at one-bit positions (Geometry::cmp): the lazy kernels, the L = 1 kernel (lva_step_acs) and the big-list kernel on
-  // the plane layout (make_geometry drops the flag where the record layout applies)
-  const bool acs = cfg->list_size == 1 && (cfg->kernel == 0 || cfg->kernel == 2) && c.nconv >= 64;
-  d->g = make_geometry(c.nconv, cfg->list_size, c.msg_bits(), (uint32_t)std::max<uint64_t>(ring, 1), lazy ? 1u : 0u, big ? 1u : 0u,
-                       (acs || big) ? 1u : 0u);
-  if (d->g.sPar >= ((uint64_t)1 << 32)) { delete d; return LVA_ERR_TOO_MANY_STATES; }
-
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) {
-    delete d;
-    return LVA_ERR_NO_DEVICE;
-  }
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) return fail(LVA_ERR_NO_DEVICE);
   d->device = cfg->device;
-  auto fail = [&](int code) { lva_decoder_destroy(d); return code; };
   if (hipSetDevice(d->device) != hipSuccess) return fail(LVA_ERR_NO_DEVICE);
   if (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess) return fail(LVA_ERR_HIP);
   for (hipEvent_t* ev : {&d->ev_total0, &d->ev_total1, &d->ev_step0, &d->ev_step1, &d->ev_h2d})
@@ -309,14 +325,6 @@ int lva_decoder_create(const lva_config* cfg, lva_decoder** out) {
   if (hipMemset(d->d_slots, 0, (size_t)slots * sizeof(SlotDesc)) != hipSuccess) return fail(LVA_ERR_HIP);
   if (hipMalloc(&d->d_steps, (size_t)slots * sizeof(SlotStep)) != hipSuccess) return fail(LVA_ERR_NOMEM);
   d->prof.slots = slots;
-  const bool fast_ok = fast_kernel_available(d->g);
-  if (cfg->kernel == 2 && !fast_ok) return fail(LVA_ERR_UNSUPPORTED);
-  // 1 = exact (one thread per target), 2 = fast + fix-up, 3 = wavefront per target (lists of 2..64 entries, and on request
-  // the wide kernel for 65..256: the default below consults the narrow predicate only, so above 64 entries it stays 1)
-  if (cfg->kernel == 3 && !wave_kernel_available(d->g) && !wave_wide_kernel_available(d->g)) return fail(LVA_ERR_UNSUPPORTED);
-  d->kernel = cfg->kernel == 1 ? 1 : cfg->kernel == 3 ? 3 : lazy ? 4 : (fast_ok ? 2 : (wave_kernel_available(d->g) ? 3 : 1));
-  if (d->kernel == 4 && (!fast_ok || c.nconv < 64)) return fail(LVA_ERR_UNSUPPORTED);
-  d->prof.kernel = d->kernel;
   // tests: force the work-list overflow path.  Honoured only together with LVA_TESTING=1 -- a stray LVA_WORK_CAP in a user's
   // environment would cost an order of magnitude silently (visible through lva_profile.overflow_steps only)
   if (const char* cap = std::getenv("LVA_WORK_CAP")) {
@@ -484,8 +492,8 @@ struct Schedule {
     sd.nblk = nblk; sd.orient = orient;
     // Lazy mode: every read starts on an EVEN launch (a read that arrives on an odd one idles for one launch: 1 in ~500),
     // so all slots are at an even time step on even launches and at an odd one on odd launches -- a launch then runs ONE
-    // instance of lva_step_lazy over a grid without workgroups of the wrong kind (launch_step_fast, phase_aligned)
-    sd.start = d->launch_no + (d->kernel == 4 ? (d->launch_no & 1u) : 0u); sd.pad = 0;
+    // instance of lva_step_lazy over a grid without workgroups of the wrong kind (launch_step, phase_aligned)
+    sd.start = d->launch_no + (d->plan.lazy ? (d->launch_no & 1u) : 0u); sd.pad = 0;
     Slot& sl = slot[s];
     sl.read = read; sl.end = sd.start + sd.nblk; sl.nblk = nblk; sl.orient = orient; sl.last_band = last_band; sl.rec = rec;
     if (sd.start != d->launch_no) ++waiting;
@@ -502,7 +510,7 @@ struct Schedule {
     StepArgs a;
     a.slots = d->d_slots; a.steps = d->d_steps; a.nslots = nslots; a.band_max = std::min<uint32_t>(npos, 2 * d->max_dev);
     a.launch_no = d->launch_no; a.step_parity = d->launch_no & 1u;
-    a.phase_aligned = d->kernel == 4 ? 1u : 0u;
+    a.phase_aligned = d->plan.lazy;
     a.full_lo = d->full_lo; a.full_hi = d->full_hi; a.pad = 0;
     {
       const int e = launch_prepare_step(a, d->d_codes, d->d_steps, d->stream);
@@ -519,16 +527,10 @@ struct Schedule {
     }
     first_step = false;
     {
-      const int e = d->kernel == 2 || d->kernel == 4
-                        ? launch_step_fast(a, d->g, d->d_codes, d->d_trellis, d->d_work, reinterpret_cast<uint32_t*>(d->d_work + 1), d->stream, e1)
-                        : d->kernel == 3 ? launch_step_wave(a, d->g, d->d_codes, d->d_trellis, d->stream)
-                                         : launch_step_exact(a, d->g, d->d_codes, d->d_trellis, d->stream);
+      const int e = launch_step(d->plan, a, d->g, d->d_codes, d->d_trellis, d->d_work, reinterpret_cast<uint32_t*>(d->d_work + 1), d->stream, e1);
       if (e) return launch_status(e);
     }
-    if (e2) {
-      if (d->kernel != 2 && d->kernel != 4) HIP_TRY(hipEventRecord(e1, d->stream));
-      HIP_TRY(hipEventRecord(e2, d->stream));
-    }
+    if (e2) HIP_TRY(hipEventRecord(e2, d->stream));
     ++d->launch_no;
     d->prof.step_launches += 1;
     d->prof.read_steps += active - waiting;

@@ -33,6 +33,7 @@ const RateDef kRates[] = {
     {1, 1, {0}}, {2, 3, {0, 2, 0}}, {3, 2, {0, 1}}, {4, 5, {0, 3, 0, 2, 1}}, {5, 3, {0, 1, 2}}, {7, 4, {0, 3, 1, 1}}};
 
 struct MemDef { int m; uint32_t g0, g1, init; };
+// (every m >= 6: the tile kernels rely on nconv = 2^m >= 64 and test it nowhere)
 const MemDef kMems[] = {                                    // :269-289
     {6, 0171, 0133, 0b100101},
     {8, 0515, 0677, 0b10010110},

@@ -132,12 +132,12 @@ struct Geometry {                // strides in 32-bit words
   uint64_t sCrf, sRing, sPar, sSlot;
 };
 
-inline Geometry make_geometry(uint32_t N, uint32_t L, uint32_t msg_bits, uint32_t R, uint32_t lazy = 0, uint32_t rec = 0, uint32_t cmp = 0) {
+// strides only: which of the layout flags go together is plan_kernels' decision (lva_plan.h), taken here as it is
+inline Geometry make_geometry(uint32_t N, uint32_t L, uint32_t msg_bits, uint32_t R, uint32_t lazy, uint32_t rec, uint32_t cmp) {
   Geometry g;
   g.N = N; g.L = L; g.P = (msg_bits + 63) / 64; if (g.P == 0) g.P = 1;
   g.W = 2 * g.P; g.F = g.W + 2; g.R = R;
-  g.lazy = lazy; g.rec = (rec && !lazy && g.P == 3 && L >= 32 && L % 4 == 0) ? 1u : 0u;   // (below 32 entries the plane layout is faster: measured)
-  g.cmp = ((lazy || cmp) && !g.rec) ? 1u : 0u;       // (the record layout keeps a list's entries together: a list that does not exist is a hole of whole lines)
+  g.lazy = lazy; g.rec = rec; g.cmp = cmp;
   g.sBlk = N * g.F;
   // lazy mode: behind the L entry blocks of a (ring, crf) list, L back-pointer bytes per conv state ([conv][entry])
   g.sCrf = (uint64_t)g.sBlk * L + (lazy ? (uint64_t)N * L / 4 : 0); g.sRing = g.sCrf * 8;

@@ -10,6 +10,7 @@
 #include "../../include/lva_decoder.h"
 #include "lva_code.h"
 #include "lva_device.h"
+#include "lva_plan.h"
 
 namespace lva {
 // the text lva_last_hip_error returns on the calling thread (lva_api.cpp owns it)
@@ -39,6 +40,7 @@ struct lva_decoder {
   std::string sync_marker;
   lva::Code code[2];           // forward, reverse complement
   uint32_t max_dev = 0;
+  lva::Plan plan{};           // which step kernel runs, on which layout (plan_kernels): decided in lva_decoder_create
   lva::Geometry g{};
   int slots = 0;
   int device = 0;
@@ -55,7 +57,6 @@ struct lva_decoder {
   size_t band_cap = 0;         // words
   lva::WorkHdr* d_work = nullptr;   // header followed by the item array
   uint32_t work_cap = 1u << 20;
-  int kernel = 1;              // 1 = exact, 2 = fast + exact fix-up
   uint32_t launch_no = 0;      // trellis-step launches since creation (the slots' clock)
   uint32_t full_lo = 1, full_hi = 0;   // positions at which every 64-source tile has a valid target (StepArgs::full_lo/hi)
   int launch_events = 0;       // lva_decoder_set_launch_events

@@ -2473,13 +2473,6 @@ __global__ void lva_gather_final(Geometry g, const DevCode* __restrict__ codes, 
 // ---------------------------------------------------------------------------------------
 // host-callable launchers (no HIP types in the signatures seen by lva_api.cpp's callers)
 // ---------------------------------------------------------------------------------------
-int launch_step_exact(const StepArgs& a, const Geometry& g, const DevCode* codes, uint32_t* trellis, void* stream) {
-  if (a.nslots == 0 || a.band_max == 0) return 0;
-  dim3 grid((g.N + 63) / 64, a.band_max, a.nslots), block(256);
-  hipLaunchKernelGGL(lva_step_exact, grid, block, 0, (hipStream_t)stream, a, g, codes, trellis);
-  return (int)hipGetLastError();
-}
-
 // f(std::integral_constant<int, V>{}) for the V of Vs that equals the run-time value v (a list size, a message plane count):
 // f's result, or hipErrorInvalidValue when v is none of them
 template <int... Vs, typename F>
@@ -2489,85 +2482,78 @@ static int with_constant(uint32_t v, F&& f) {
   return e;
 }
 
-int launch_step_wave(const StepArgs& a, const Geometry& g, const DevCode* codes, uint32_t* trellis, void* stream) {
-  if (a.nslots == 0 || a.band_max == 0) return 0;
-  dim3 grid((g.N + 3) / 4, a.band_max * 8, a.nslots), block(256);
-  if (g.L <= 64) {
-    hipLaunchKernelGGL(lva_step_wave, grid, block, 0, (hipStream_t)stream, a, g, codes, trellis);
-    return (int)hipGetLastError();
-  }
-  return with_constant<2, 3, 4>((g.L + 63) / 64, [&](auto r) {       // register rows of 64 entries
-    hipLaunchKernelGGL((lva_step_wave_wide<decltype(r)::value>), grid, block, 0, (hipStream_t)stream, a, g, codes, trellis);
-    return (int)hipGetLastError();
-  });
-}
-
-bool wave_kernel_available(const Geometry& g) { return g.L >= 2 && g.L <= 64; }
-bool wave_wide_kernel_available(const Geometry& g) { return g.L > 64 && g.L <= 256; }
-
-static bool small_list(const Geometry& g) { return g.L == 1 || g.L == 2 || g.L == 4 || g.L == 8; }
-
-bool fast_kernel_available(const Geometry& g) {
-  const bool l_ok = small_list(g) || (g.L >= 2 && g.L <= 64);
-  return l_ok && g.P >= 1 && g.P <= 4 && g.N >= 64;
-}
-
-int launch_step_fast(const StepArgs& a, const Geometry& g, const DevCode* codes, uint32_t* trellis, WorkHdr* hdr,
-                     uint32_t* items, void* stream, void* ev_mid) {
-  if (a.nslots == 0 || a.band_max == 0) return 0;
+int launch_step(const Plan& plan, const StepArgs& a, const Geometry& g, const DevCode* codes, uint32_t* trellis, WorkHdr* hdr,
+                uint32_t* items, void* stream, void* ev_mid) {
   hipStream_t st = (hipStream_t)stream;
+  if (a.nslots == 0 || a.band_max == 0) return ev_mid ? (int)hipEventRecord((hipEvent_t)ev_mid, st) : 0;
+  // every step kernel takes (a, g, codes, trellis), the fast ones and the fix-up passes the work list behind them
+  auto run = [&](auto kernel, dim3 grid, dim3 block, auto... work_list) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, a, g, codes, trellis, work_list...);
+    return (int)hipGetLastError();
+  };
+  auto with_planes = [&](auto&& f) { return with_constant<1, 2, 3, 4>(g.P, f); };   // (msg_len + mem_conv <= 256 bits: at most four)
   const dim3 grid(g.N / TS, a.band_max, a.nslots), grid_big(g.N / TSB, a.band_max, a.nslots);
+  const dim3 grid_wave((g.N + 3) / 4, a.band_max * 8, a.nslots);
   // 1. the dominant kernel
-  int e;
-  if (!small_list(g) && g.rec) {   // big-list kernel, record layout (three message planes, 32 <= L <= 64, L a multiple of 4)
-    if (g.L <= 32) hipLaunchKernelGGL((lva_step_big_rec<32>), grid_big, dim3(8 * TSB), 0, st, a, g, codes, trellis, hdr, items);
-    else hipLaunchKernelGGL((lva_step_big_rec<64>), grid_big, dim3(8 * TSB), 0, st, a, g, codes, trellis, hdr, items);
-    e = (int)hipGetLastError();
-  } else if (!small_list(g)) {     // big-list kernel, plane layout
-    e = with_constant<1, 2, 3, 4>(g.P, [&](auto p) {
-      constexpr int P = decltype(p)::value;
-      if (g.L <= 16) hipLaunchKernelGGL((lva_step_big<16, P>), grid_big, dim3(8 * TSB), 0, st, a, g, codes, trellis, hdr, items);
-      else if (g.L <= 32) hipLaunchKernelGGL((lva_step_big<32, P>), grid_big, dim3(8 * TSB), 0, st, a, g, codes, trellis, hdr, items);
-      else hipLaunchKernelGGL((lva_step_big<64, P>), grid_big, dim3(8 * TSB), 0, st, a, g, codes, trellis, hdr, items);
-      return (int)hipGetLastError();
-    });
-  } else if (g.lazy) {
-    // phase-aligned slots (the host starts every read on an even launch): all slots are at an even time step on even launches
-    // and at an odd one on odd launches -- one instance per launch, no workgroups of the wrong kind
-    const bool run_anchor = !a.phase_aligned || !(a.launch_no & 1u), run_odd = !a.phase_aligned || (a.launch_no & 1u);
-    e = with_constant<2, 4, 8>(g.L, [&](auto ll) {
-      return with_constant<1, 2, 3, 4>(g.P, [&](auto p) {
-        constexpr int LL = decltype(ll)::value, P = decltype(p)::value;
-        if (run_anchor) hipLaunchKernelGGL((lva_step_lazy<LL, P, true>), grid, dim3(8 * TS), 0, st, a, g, codes, trellis, hdr, items);
-        if (run_odd) hipLaunchKernelGGL((lva_step_lazy<LL, P, false>), grid, dim3(8 * TS), 0, st, a, g, codes, trellis, hdr, items);
-        return (int)hipGetLastError();
+  int e = (int)hipErrorInvalidValue;
+  switch (plan.dominant) {
+    case StepKernel::Exact:
+      e = run(lva_step_exact, dim3((g.N + 63) / 64, a.band_max, a.nslots), dim3(256));
+      break;
+    case StepKernel::Wave:
+      e = run(lva_step_wave, grid_wave, dim3(256));
+      break;
+    case StepKernel::WaveWide:       // register rows of 64 entries
+      e = with_constant<2, 3, 4>((uint32_t)plan.inst, [&](auto r) { return run(lva_step_wave_wide<decltype(r)::value>, grid_wave, dim3(256)); });
+      break;
+    case StepKernel::Acs:
+      e = with_planes([&](auto p) { return run(lva_step_acs<decltype(p)::value>, grid, dim3(4 * TS)); });
+      break;
+    case StepKernel::Fast:
+      e = with_constant<2, 4, 8>(g.L, [&](auto ll) {
+        return with_planes([&](auto p) { return run(lva_step_fast<decltype(ll)::value, decltype(p)::value>, grid, dim3(8 * TS), hdr, items); });
       });
-    });
-  } else if (g.L == 1) {
-    e = with_constant<1, 2, 3, 4>(g.P, [&](auto p) {
-      hipLaunchKernelGGL((lva_step_acs<decltype(p)::value>), grid, dim3(4 * TS), 0, st, a, g, codes, trellis);
-      return (int)hipGetLastError();
-    });
-  } else {
-    e = with_constant<2, 4, 8>(g.L, [&](auto ll) {
-      return with_constant<1, 2, 3, 4>(g.P, [&](auto p) {
-        constexpr int LL = decltype(ll)::value, P = decltype(p)::value;
-        hipLaunchKernelGGL((lva_step_fast<LL, P>), grid, dim3(8 * TS), 0, st, a, g, codes, trellis, hdr, items);
-        return (int)hipGetLastError();
+      break;
+    case StepKernel::Lazy: {
+      // phase-aligned slots (the host starts every read on an even launch): all slots are at an even time step on even launches
+      // and at an odd one on odd launches -- one instance per launch, no workgroups of the wrong kind
+      const bool run_anchor = !a.phase_aligned || !(a.launch_no & 1u), run_odd = !a.phase_aligned || (a.launch_no & 1u);
+      e = with_constant<2, 4, 8>(g.L, [&](auto ll) {
+        return with_planes([&](auto p) {
+          constexpr int LL = decltype(ll)::value, P = decltype(p)::value;
+          int el = 0;
+          if (run_anchor) el = run(lva_step_lazy<LL, P, true>, grid, dim3(8 * TS), hdr, items);
+          if (run_odd && !el) el = run(lva_step_lazy<LL, P, false>, grid, dim3(8 * TS), hdr, items);
+          return el;
+        });
       });
-    });
+      break;
+    }
+    case StepKernel::Big:            // big-list kernel, plane layout
+      e = with_constant<16, 32, 64>((uint32_t)plan.inst, [&](auto ll) {
+        return with_planes([&](auto p) { return run(lva_step_big<decltype(ll)::value, decltype(p)::value>, grid_big, dim3(8 * TSB), hdr, items); });
+      });
+      break;
+    case StepKernel::BigRec:         // big-list kernel, record layout
+      e = with_constant<32, 64>((uint32_t)plan.inst, [&](auto ll) { return run(lva_step_big_rec<decltype(ll)::value>, grid_big, dim3(8 * TSB), hdr, items); });
+      break;
   }
   if (e) return e;
   if (ev_mid && (e = (int)hipEventRecord((hipEvent_t)ev_mid, st))) return e;
-  // 2. the fix-up pass over the work list (exits at once when it is empty); L = 1 has no ties to resolve, no work list
-  if (g.L == 1) return 0;
-  if (g.lazy && small_list(g))     // one target per wavefront and pass: the pass is a chain of dependent round trips, so more
-    return with_constant<1, 2, 3, 4>(g.P, [&](auto p) {   // (mostly idle) wavefronts, not fewer
-      hipLaunchKernelGGL((lva_step_fixup_lazy<decltype(p)::value>), dim3(kFixupLazyGrid), dim3(256), 0, st, a, g, codes, trellis, hdr, items);
-      return (int)hipGetLastError();
-    });
-  hipLaunchKernelGGL(lva_step_fixup_wave, dim3(4096), dim3(256), 0, st, a, g, codes, trellis, hdr, items);
-  return (int)hipGetLastError();
+  // 2. the fix-up pass over the work list (exits at once when it is empty)
+  switch (plan.fixup) {
+    case Fixup::None:
+      break;
+    case Fixup::Wave:
+      e = run(lva_step_fixup_wave, dim3(4096), dim3(256), hdr, items);
+      break;
+    case Fixup::Lazy:                // one target per wavefront and pass: the pass is a chain of dependent round trips, so more
+      e = with_planes([&](auto p) {   // (mostly idle) wavefronts, not fewer
+        return run(lva_step_fixup_lazy<decltype(p)::value>, dim3(kFixupLazyGrid), dim3(256), hdr, items);
+      });
+      break;
+  }
+  return e;
 }
 
 int launch_prepare_step(const StepArgs& a, const DevCode* codes, SlotStep* steps, void* stream) {

@@ -64,6 +64,22 @@ def code_tables(mem_conv, rate, msg_len, rc=False, sync_marker="", sync_period=0
     return dict(pos2msg=pos2msg, ptype=ptype, vmask=vmask, vval=vval, predtab=predtab)
 
 
+STEP_KERNELS = ("exact", "wave", "wave_wide", "acs", "fast", "lazy", "big", "big_rec")     # LVA_STEP_* of include/lva_decoder.h
+FIXUP_KERNELS = ("none", "wave", "lazy")                                                    # LVA_FIXUP_*
+
+
+def kernel_plan(mem_conv, rate, msg_len, list_size=1, max_deviation=None, sync_marker="", sync_period=0, kernel=0):
+    """What a Decoder of these arguments runs, decided without a device (lva_kernel_plan): dict(mode = the kernel mode that
+    profile()["kernel"] reports, dominant and fixup = names out of STEP_KERNELS / FIXUP_KERNELS, lazy / rec / cmp = the layout
+    flags, ring_positions, instance).  Raises the LvaError the Decoder would raise before it looks for a GPU."""
+    cfg = _lib.Config(mem_conv, rate, msg_len, list_size, _lib.MAX_DEVIATION_DEFAULT if max_deviation is None else max_deviation,
+                      _sm(sync_marker), sync_period, 0, 0, kernel, 0)
+    s = _lib.KernelPlanInfo()
+    check(load_library().lva_kernel_plan(ctypes.byref(cfg), ctypes.byref(s)), detail=None)
+    return dict(mode=s.mode, dominant=STEP_KERNELS[s.dominant], fixup=FIXUP_KERNELS[s.fixup], lazy=s.lazy, rec=s.rec, cmp=s.cmp,
+                ring_positions=s.ring_positions, instance=s.instance)
+
+
 def band_table(mem_conv, rate, msg_len, nblk, max_deviation=None, rc=False, sync_marker="", sync_period=0):
     """-> (reference, working): int arrays [nblk, 2] of [lo, hi) per time step -- the reference's band (:677-679) and the band the
     kernels work on (without positions whose lists cannot reach the output; include/lva_decoder.h lva_band_table)."""
@@ -111,11 +127,12 @@ def algorithmic_bytes(mem_conv, rate, msg_len, nblk, list_size, max_deviation=No
 class Decoder:
     """A list-Viterbi decoder bound to one GPU.  Fails loudly without a GPU (no CPU path).
 
-    kernel: 0 = default (the fastest mode for the configuration: 4 for list sizes 2 / 4 / 8 with up to 192 message bits,
+    kernel: 0 = default (the fastest mode for the configuration: 4 for list sizes 2 / 4 / 8,
     else 2 for list sizes up to 64, the thread-per-target exact kernel beyond), 1 = thread-per-target exact kernel,
     2 = fast kernel + exact fix-up, 3 = wavefront-per-target exact kernel (list sizes 2..256; above 64 entries it is the one
     alternative to mode 1 and has to be asked for), 4 = fast kernel with lazy messages
-    (materialised every second time step).  All modes give the reference's lists bit for bit; they differ in speed only."""
+    (materialised every second time step); kernel_plan(...) tells what a configuration resolves to.  All modes give the
+    reference's lists bit for bit; they differ in speed only."""
 
     def __init__(self, mem_conv, rate, msg_len, list_size=1, max_deviation=None, sync_marker="", sync_period=0,
                  device=0, max_slots=0, kernel=0, mem_budget_bytes=0):

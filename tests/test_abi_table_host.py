@@ -19,7 +19,7 @@ SCALARS = {"int": (4, True, False), "int32_t": (4, True, False), "uint32_t": (4,
 # header structure -> Python class
 STRUCTS = {"lva_config": _lib.Config, "lva_code_info": _lib.CodeInfoStruct, "lva_profile": _lib.Profile,
            "lva_payload_pos": _lib.PayloadPos, "lva_experiment_barcodes": _lib.ExperimentBarcodes, "lva_demux_pos": _lib.DemuxPos,
-           "lva_list_stat": _lib.ListStat}
+           "lva_list_stat": _lib.ListStat, "lva_kernel_plan_info": _lib.KernelPlanInfo}
 
 
 def _header():

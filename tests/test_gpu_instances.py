@@ -1,5 +1,5 @@
 """Kernel instances and slot configurations no other test launches: every instance of the
-dispatcher in launch_step_fast (lva_kernels.hip) runs at least once against the CPU oracle or the reference's own lists."""
+dominant-kernel switch of launch_step (lva_kernels.hip) runs at least once against the CPU oracle or the reference's own lists."""
 import numpy as np
 import pytest
 
