@@ -463,6 +463,46 @@ typedef struct lva_list_stat {
 int lva_list_stats(int32_t device, const uint8_t *msgs, const int32_t *counts, const uint8_t *truth, int32_t n_reads,
                    int32_t list_size, uint32_t msg_len, lva_list_stat *out);
 
+/* ---------------------------------------------------------------------------------------------
+ * reads made on the device, in front of lva_transpost_batch_device -- random message ->
+ * lva_encode's oligo of the decoder's (mem_conv, rate, msg_len) -> strand -> insertion / deletion / substitution channel
+ * -> flip-flop path and dwells -> transition scores in the layout above.  Every draw is a word of Philox4x32-10 under
+ * key = seed and counter (item, sub, read number, stream): read number k = first_read + index is the same read in every
+ * batch, launch shape and device.  nanopore_dna_storage_amd/simulate.py restates the rules in numpy and is the definition.
+ * Shared arguments:
+ *   sub_thr, del_thr, ins_thr  floor(p * 2^32) of the channel probabilities, each at most 2^30 (p <= 0.25);
+ *   dwell_cdf [dwell_k]        1..64 entries; a base has d extra blocks, d = the first d with word < dwell_cdf[d], else dwell_k;
+ *   start_barcode, end_barcode both NULL: the strand is the oligo.  Both given (1..64 characters of ACGT): flank + start
+ *                              barcode + oligo + end barcode + flank, flank lengths uniform in [flank_lo, flank_hi],
+ *                              flank_hi <= 256, and at most 1024 bases in all;
+ *   rc_mode                    0: no strand is reverse-complemented before the channel, 1: all, 2: odd read numbers.
+ * first_read + n_reads <= 2^32.  A decoder created with a sync marker is refused with LVA_ERR_UNSUPPORTED (lva_encode
+ * takes none).  Refusals in this order, all before the device is touched: own arguments, barcodes, LVA_ERR_BUSY while a
+ * decode stream is open, nothing to do (n_reads = 0), device.  Both calls run on the decoder's stream and are complete on
+ * return.
+ * ------------------------------------------------------------------------------------------- */
+
+/* The lengths-only pass: row_offsets_out / base_offsets_out [n_reads + 1] = block and base offsets of the batch (first 0).
+ * LVA_ERR_ARG if the batch exceeds what the other stages take (2^20 blocks per read, 2^31 in all). */
+int lva_simulate_plan(lva_decoder *d, uint64_t seed, uint32_t first_read, int32_t n_reads, uint32_t sub_thr, uint32_t del_thr,
+                      uint32_t ins_thr, const uint32_t *dwell_cdf, int32_t dwell_k, const char *start_barcode,
+                      const char *end_barcode, uint32_t flank_lo, uint32_t flank_hi, int32_t rc_mode, int64_t *row_offsets_out,
+                      int64_t *base_offsets_out);
+/* The fill pass with the plan's offsets: scores_dev [row_offsets[n_reads]][40] float32 on the decoder's device, 16-byte
+ * aligned, = clip(float32(s - 131070) * scale (+ margin on the block's true transition), -clip, clip), s the sum of four
+ * 16-bit halves of the noise words; three separately rounded float32 operations.  scale = float32(sigma * sqrt(3) / 65536)
+ * gives noise of standard deviation sigma.  clip > 0.  Truth to the host: msgs_out uint8 [n_reads][msg_len]; bases_out
+ * uint8 [base_offsets[n_reads]] (0..3, what the channel emitted) and true_idx_out uint8 [row_offsets[n_reads]] (the true
+ * transition of every block) or NULL.  Offsets that are not the plan's of the same arguments: LVA_ERR_ARG, with nothing
+ * written outside them.  Fewer than 2^32 / 10 blocks.  Afterwards lva_decoder_profile reports total_ms = HIP-event time of
+ * the score kernel and read_steps = blocks. */
+int lva_simulate_fill_device(lva_decoder *d, uint64_t seed, uint32_t first_read, int32_t n_reads, uint32_t sub_thr,
+                             uint32_t del_thr, uint32_t ins_thr, const uint32_t *dwell_cdf, int32_t dwell_k,
+                             const char *start_barcode, const char *end_barcode, uint32_t flank_lo, uint32_t flank_hi,
+                             int32_t rc_mode, float scale, float margin, float clip, const int64_t *row_offsets,
+                             const int64_t *base_offsets, float *scores_dev, uint8_t *msgs_out, uint8_t *bases_out,
+                             uint8_t *true_idx_out);
+
 #ifdef __cplusplus
 }
 #endif

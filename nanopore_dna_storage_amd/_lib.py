@@ -87,6 +87,9 @@ _i32, _u32, _u64, _u16 = ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint64, ctype
 _code = [_i32, _i32, _u32, _i32, _cp, _u32]          # mem_conv, rate, msg_len, rc, sync_marker, sync_period
 _decode_out = [_vp, _vp, _vp, _vp]                   # rc_flags, out_msgs, out_scores, out_counts
 _demux = [_vp, _i32, _i32, _i32, _vp, _vp]           # exps, n_exps, max_dist, min_margin, out, all_out
+_f32 = ctypes.c_float
+# d, seed, first_read, n_reads, sub / del / ins thresholds, dwell_cdf, dwell_k, barcodes, flank_lo, flank_hi, rc_mode
+_sim = [_vp, _u64, _u32, _i32, _u32, _u32, _u32, _vp, _i32, _cp, _cp, _u32, _u32, _i32]
 
 # The C ABI, once: every function include/lva_decoder.h declares -> (restype, argtypes), in the header's order
 # (tests/test_abi_table_host.py parses the header and holds this table and the structures above to it)
@@ -134,6 +137,8 @@ ABI = {
     "lva_list_filter": (_int, [_i32, _vp, _vp, _i32, _i32, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "lva_list_consensus": (_int, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "lva_list_stats": (_int, [_i32, _vp, _vp, _vp, _i32, _i32, _u32, _vp]),
+    "lva_simulate_plan": (_int, _sim + [_vp, _vp]),
+    "lva_simulate_fill_device": (_int, _sim + [_f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTS = list(ABI)
 

@@ -8,6 +8,7 @@
 #include "bc_kernels.h"
 #include "tp_kernels.h"
 #include "ls_kernels.h"
+#include "sim_kernels.h"
 
 using namespace lva;
 
@@ -548,6 +549,169 @@ int lva_list_stats(int32_t device, const uint8_t* msgs, const int32_t* counts, c
   if (e) return launch_status(e);
   HIP_TRY(hipMemcpyAsync(out, arena.ptr(d_out), 4 * kLsStatFields * n, hipMemcpyDeviceToHost, st.s));
   return drain.finish();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// the read simulator (csrc/sim_kernels.hip; the definition is simulate.py).
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+static_assert(kSimMaxBarcode == kMaxBarcode, "a simulated barcode is one the searches accept");
+
+struct SimCall {
+  SimParams p{};
+  std::vector<uint16_t> posinfo;          // per oligo position: message bits consumed before it | block type << 12
+  uint8_t bc[2 * kSimMaxBarcode] = {0};   // start barcode, end barcode as 0..3
+};
+
+// a call's own arguments, the barcodes apart: everything both entry points share
+int sim_args(lva_decoder* d, uint64_t seed, uint32_t first_read, int32_t n, uint32_t sub_thr, uint32_t del_thr, uint32_t ins_thr,
+             const uint32_t* dwell_cdf, int32_t dwell_k, int32_t rc_mode, SimCall* c) {
+  if (!d || n < 0 || !dwell_cdf || dwell_k < 1 || dwell_k > kSimMaxDwell || rc_mode < 0 || rc_mode > 2) return LVA_ERR_ARG;
+  if ((uint64_t)first_read + (uint64_t)n > ((uint64_t)1 << 32)) return LVA_ERR_ARG;        // read numbers are 32-bit
+  if (sub_thr > kSimMaxThreshold || del_thr > kSimMaxThreshold || ins_thr > kSimMaxThreshold) return LVA_ERR_ARG;
+  if (!d->sync_marker.empty()) return LVA_ERR_UNSUPPORTED;                                 // lva_encode takes no marker
+  const Code& code = d->code[0];
+  SimParams& p = c->p;
+  p.k0 = (uint32_t)seed; p.k1 = (uint32_t)(seed >> 32);
+  p.first_read = first_read;
+  p.thr_sub = sub_thr; p.thr_del = del_thr; p.thr_ins = ins_thr;
+  p.dwell_k = (uint32_t)dwell_k;
+  p.msg_len = code.msg_len; p.mem_conv = (uint32_t)code.mem_conv;
+  p.g0 = code.g[0]; p.g1 = code.g[1]; p.init = code.init; p.fin = code.fin;
+  p.oligo_len = code.oligo_len();
+  p.rc_mode = (uint32_t)rc_mode;
+  c->posinfo.resize(p.oligo_len);
+  for (uint32_t pos = 0; pos < p.oligo_len; ++pos)
+    c->posinfo[pos] = (uint16_t)(code.pos2msg[pos] | (uint32_t)code.pattern[pos % (uint32_t)code.plen] << 12);
+  return LVA_OK;
+}
+
+bool sim_barcode(const char* s, uint8_t* dst, uint32_t* len) {
+  const size_t n = std::strlen(s);
+  if (n == 0 || n > (size_t)kSimMaxBarcode) return false;
+  for (size_t i = 0; i < n; ++i) {
+    const char* at = std::strchr("ACGT", s[i]);
+    if (!at) return false;
+    dst[i] = (uint8_t)(at - "ACGT");
+  }
+  *len = (uint32_t)n;
+  return true;
+}
+
+// both barcodes or neither; with them the flank range and the length of the longest strand
+int sim_barcodes(const char* start_bc, const char* end_bc, uint32_t flank_lo, uint32_t flank_hi, SimCall* c) {
+  if (!start_bc && !end_bc) return LVA_OK;
+  if (!start_bc || !end_bc) return LVA_ERR_ARG;
+  SimParams& p = c->p;
+  if (!sim_barcode(start_bc, c->bc, &p.len_start) || !sim_barcode(end_bc, c->bc + kSimMaxBarcode, &p.len_end)) return LVA_ERR_ARG;
+  if (flank_lo > flank_hi || flank_hi > (uint32_t)kSimMaxFlank) return LVA_ERR_ARG;
+  if (2 * flank_hi + p.len_start + p.len_end + p.oligo_len > (uint32_t)kSimMaxStrand) return LVA_ERR_ARG;
+  p.barcoded = 1; p.flank_lo = flank_lo; p.flank_span = flank_hi - flank_lo + 1;
+  return LVA_OK;
+}
+
+struct SimTables {
+  Arena::Piece<uint16_t> posinfo;
+  Arena::Piece<uint32_t> cdf;
+  Arena::Piece<uint8_t> bc;
+};
+SimTables sim_tables(Arena& a, const SimCall& c) {
+  return {a.add<uint16_t>(c.posinfo.size()), a.add<uint32_t>(c.p.dwell_k), a.add<uint8_t>(sizeof c.bc)};
+}
+// c and dwell_cdf outlive the call's StreamDrain
+int upload_sim_tables(lva_decoder* d, const Arena& a, const SimTables& t, const SimCall& c, const uint32_t* dwell_cdf) {
+  HIP_TRY(hipMemcpyAsync(a.ptr(t.posinfo), c.posinfo.data(), 2 * c.posinfo.size(), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(a.ptr(t.cdf), dwell_cdf, 4 * (size_t)c.p.dwell_k, hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(a.ptr(t.bc), c.bc, sizeof c.bc, hipMemcpyHostToDevice, d->stream));
+  return LVA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lva_simulate_plan(lva_decoder* d, uint64_t seed, uint32_t first_read, int32_t n_reads, uint32_t sub_thr, uint32_t del_thr,
+                      uint32_t ins_thr, const uint32_t* dwell_cdf, int32_t dwell_k, const char* start_barcode,
+                      const char* end_barcode, uint32_t flank_lo, uint32_t flank_hi, int32_t rc_mode, int64_t* row_offsets_out,
+                      int64_t* base_offsets_out) {
+  SimCall c;
+  int st = sim_args(d, seed, first_read, n_reads, sub_thr, del_thr, ins_thr, dwell_cdf, dwell_k, rc_mode, &c);
+  if (st == LVA_OK && (!row_offsets_out || !base_offsets_out)) st = LVA_ERR_ARG;
+  if (st != LVA_OK) return st;
+  if ((st = sim_barcodes(start_barcode, end_barcode, flank_lo, flank_hi, &c)) != LVA_OK) return st;
+  st = stage_enter(d, n_reads == 0);
+  if (st == LVA_OK) row_offsets_out[0] = base_offsets_out[0] = 0;
+  if (st != kRun) return st;
+  const size_t n = (size_t)n_reads;
+  std::vector<int32_t> lens(2 * n);
+  Arena arena;
+  const SimTables tab = sim_tables(arena, c);
+  const auto d_lens = arena.add<int32_t>(2 * n);
+  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
+  StreamDrain drain(d->stream);
+  if ((st = upload_sim_tables(d, arena, tab, c, dwell_cdf)) != LVA_OK) return st;
+  const int e = launch_sim_strand(c.p, n_reads, arena.ptr(tab.posinfo), arena.ptr(tab.cdf), arena.ptr(tab.bc), nullptr, nullptr,
+                                  arena.ptr(d_lens), nullptr, nullptr, nullptr, nullptr, d->stream);
+  if (e) return launch_status(e);
+  HIP_TRY(hipMemcpyAsync(lens.data(), arena.ptr(d_lens), 8 * n, hipMemcpyDeviceToHost, d->stream));
+  if ((st = drain.finish()) != LVA_OK) return st;
+  row_offsets_out[0] = base_offsets_out[0] = 0;
+  for (size_t i = 0; i < n; ++i) {
+    base_offsets_out[i + 1] = base_offsets_out[i] + lens[2 * i];
+    row_offsets_out[i + 1] = row_offsets_out[i] + lens[2 * i + 1];
+  }
+  size_t T = 0;                                                   // a batch the other stages would refuse is refused here
+  return check_offsets(row_offsets_out, n_reads, &T);
+}
+
+int lva_simulate_fill_device(lva_decoder* d, uint64_t seed, uint32_t first_read, int32_t n_reads, uint32_t sub_thr,
+                             uint32_t del_thr, uint32_t ins_thr, const uint32_t* dwell_cdf, int32_t dwell_k,
+                             const char* start_barcode, const char* end_barcode, uint32_t flank_lo, uint32_t flank_hi,
+                             int32_t rc_mode, float scale, float margin, float clip, const int64_t* row_offsets,
+                             const int64_t* base_offsets, float* scores_dev, uint8_t* msgs_out, uint8_t* bases_out,
+                             uint8_t* true_idx_out) {
+  SimCall c;
+  int st = sim_args(d, seed, first_read, n_reads, sub_thr, del_thr, ins_thr, dwell_cdf, dwell_k, rc_mode, &c);
+  if (st != LVA_OK) return st;
+  if (!row_offsets || !base_offsets || !(clip > 0.0f) || scale != scale || margin != margin) return LVA_ERR_ARG;
+  size_t T = 0, B = 0;
+  if (check_offsets(row_offsets, n_reads, &T) != LVA_OK || check_offsets(base_offsets, n_reads, &B) != LVA_OK) return LVA_ERR_ARG;
+  if ((uint64_t)T * 10 >= ((uint64_t)1 << 32)) return LVA_ERR_ARG;              // sim_scores counts 16-byte quads in 32 bits
+  if (n_reads > 0 && (!scores_dev || ((uintptr_t)scores_dev & 15u) || !msgs_out)) return LVA_ERR_ARG;
+  if ((st = sim_barcodes(start_barcode, end_barcode, flank_lo, flank_hi, &c)) != LVA_OK) return st;
+  st = stage_enter(d, n_reads == 0);
+  if (st != kRun) return st;
+  const size_t n = (size_t)n_reads, mb = n * c.p.msg_len;
+  int32_t bad = 0;
+  Arena arena;
+  const SimTables tab = sim_tables(arena, c);
+  const auto d_row = arena.add<int64_t>(n + 1), d_base = arena.add<int64_t>(n + 1);
+  const auto d_msgs = arena.add<uint8_t>(mb), d_bases = arena.add<uint8_t>(B), d_tidx = arena.add<uint8_t>(T);
+  const auto d_bad = arena.add<int32_t>(1);
+  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
+  StreamDrain drain(d->stream);
+  if ((st = upload_sim_tables(d, arena, tab, c, dwell_cdf)) != LVA_OK) return st;
+  HIP_TRY(hipMemcpyAsync(arena.ptr(d_row), row_offsets, 8 * (n + 1), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(arena.ptr(d_base), base_offsets, 8 * (n + 1), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemsetAsync(arena.ptr(d_bad), 0, sizeof(int32_t), d->stream));
+  int e = launch_sim_strand(c.p, n_reads, arena.ptr(tab.posinfo), arena.ptr(tab.cdf), arena.ptr(tab.bc), arena.ptr(d_row),
+                            arena.ptr(d_base), nullptr, arena.ptr(d_msgs), arena.ptr(d_bases), arena.ptr(d_tidx), arena.ptr(d_bad),
+                            d->stream);
+  if (e) return launch_status(e);
+  HIP_TRY(hipEventRecord(d->ev_total0, d->stream));
+  e = launch_sim_scores(c.p, n_reads, arena.ptr(d_row), (uint32_t)T, arena.ptr(d_tidx), scale, margin, clip, scores_dev, d->stream);
+  if (e) return launch_status(e);
+  HIP_TRY(hipEventRecord(d->ev_total1, d->stream));
+  HIP_TRY(hipMemcpyAsync(msgs_out, arena.ptr(d_msgs), mb, hipMemcpyDeviceToHost, d->stream));
+  if (bases_out && B) HIP_TRY(hipMemcpyAsync(bases_out, arena.ptr(d_bases), B, hipMemcpyDeviceToHost, d->stream));
+  if (true_idx_out && T) HIP_TRY(hipMemcpyAsync(true_idx_out, arena.ptr(d_tidx), T, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipMemcpyAsync(&bad, arena.ptr(d_bad), sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
+  if ((st = drain.finish()) != LVA_OK) return st;
+  if ((st = tp_profile(d, T, true)) != LVA_OK) return st;
+  return bad ? LVA_ERR_ARG : LVA_OK;           // the offsets are not this call's plan: nothing was written outside them
 }
 
 }  // extern "C"

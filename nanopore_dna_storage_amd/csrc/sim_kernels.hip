@@ -1,0 +1,256 @@
+// sim_kernels.hip -- the read simulator on the device: message -> oligo -> strand -> channel ->
+// flip-flop path and dwells (sim_strand), transition scores (sim_scores).  Every draw is a word of Philox4x32-10 under the
+// counter (item, sub, read number, stream); nanopore_dna_storage_amd/simulate.py says which word serves which draw and
+// is what these kernels are held to, bit for bit.  No floating-point number takes part in a decision, and the score
+// arithmetic is three separately rounded float32 operations (the library is built with -ffp-contract=off).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "sim_kernels.h"
+
+namespace lva {
+
+namespace {
+
+constexpr uint32_t kM0 = 0xD2511F53u, kM1 = 0xCD9E8D57u, kW0 = 0x9E3779B9u, kW1 = 0xBB67AE85u;
+constexpr uint32_t kStreamMessage = 0, kStreamChannel = 1, kStreamDwell = 2, kStreamNoise = 3, kStreamLead = 4;
+constexpr int kSimMaxEmit = 5 * kSimMaxStrand + 4;     // 4 insertions + the base per position, 4 more behind the last
+constexpr int kSimMaxBits = 544;                       // mem_conv initial bits + message + termination (2 * 255 + 14 at most)
+
+struct U4 { uint32_t x, y, z, w; };
+
+__device__ __forceinline__ U4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t h0 = __umulhi(kM0, c0), l0 = kM0 * c0, h1 = __umulhi(kM1, c2), l1 = kM1 * c2;
+    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+    k0 += kW0; k1 += kW1;
+  }
+  return {c0, c1, c2, c3};
+}
+
+__device__ __forceinline__ uint32_t pick(const U4& v, uint32_t i) {      // v[i] without an indexed register array
+  return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w;
+}
+
+// inclusive scans over the wavefront
+__device__ __forceinline__ int wave_scan_add(int v, int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int t = __shfl_up(v, d, 64);
+    if (lane >= d) v += t;
+  }
+  return v;
+}
+__device__ __forceinline__ int wave_scan_max(int v, int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int t = __shfl_up(v, d, 64);
+    if (lane >= d) v = max(v, t);
+  }
+  return v;
+}
+
+__device__ __forceinline__ uint32_t transition_index(uint32_t frm, uint32_t to) { return to < 4 ? to * 8 + frm : 32 + frm; }
+
+// One workgroup of one wavefront per read; lane = position, 64 positions per pass.
+__global__ __launch_bounds__(64) void sim_strand(SimParams p, const uint16_t* __restrict__ posinfo, const uint32_t* __restrict__ cdf,
+                                                 const uint8_t* __restrict__ bc, const int64_t* __restrict__ row_off,
+                                                 const int64_t* __restrict__ base_off, int32_t* __restrict__ lens,
+                                                 uint8_t* __restrict__ msgs, uint8_t* __restrict__ bases,
+                                                 uint8_t* __restrict__ true_idx, int32_t* __restrict__ bad) {
+  __shared__ uint8_t xb[kSimMaxBits];        // the register's bit sequence: initial state, message, termination
+  __shared__ uint8_t src[kSimMaxStrand];     // the strand the channel reads
+  __shared__ uint8_t em[kSimMaxEmit + 60];   // the bases it emits
+  __shared__ uint32_t s_cdf[kSimMaxDwell];
+  const int lane = (int)threadIdx.x;
+  const uint32_t r = blockIdx.x, R = p.first_read + r;
+  const bool fill = row_off != nullptr;
+  const uint32_t m = p.mem_conv, total = p.msg_len + m;
+
+  // ---- message (stream 0) and the bits around it
+  for (uint32_t jp = (uint32_t)lane; jp < total + m; jp += 64) {
+    uint32_t bit;
+    if (jp < m) {
+      bit = (p.init >> jp) & 1u;
+    } else if (jp - m < p.msg_len) {
+      const uint32_t i = jp - m;
+      const U4 w = philox(i >> 7, 0, R, kStreamMessage, p.k0, p.k1);
+      bit = (pick(w, (i >> 5) & 3u) >> (i & 31u)) & 1u;
+      if (fill) msgs[(size_t)r * p.msg_len + i] = (uint8_t)bit;
+    } else {
+      bit = (p.fin >> (jp - m - p.msg_len)) & 1u;
+    }
+    xb[jp] = (uint8_t)bit;
+  }
+  if ((uint32_t)lane < p.dwell_k) s_cdf[lane] = cdf[lane];
+  __syncthreads();
+
+  // ---- strand: the oligo alone, or flank + start barcode + oligo + end barcode + flank (stream 4), reverse complement
+  const U4 L = philox(0, 0, R, kStreamLead, p.k0, p.k1);
+  uint32_t f5 = 0, f3 = 0, o0 = 0, n = p.oligo_len;
+  if (p.barcoded) {
+    f5 = p.flank_lo + __umulhi(L.y, p.flank_span);
+    f3 = p.flank_lo + __umulhi(L.z, p.flank_span);
+    o0 = f5 + p.len_start;
+    n = o0 + p.oligo_len + p.len_end + f3;
+  }
+  const bool rc = p.rc_mode == 1 || (p.rc_mode == 2 && (R & 1u));
+  for (uint32_t i = (uint32_t)lane; i < n; i += 64) {
+    uint32_t b;
+    if (i < f5 || i >= n - f3) {
+      const U4 w = philox(1 + (i >> 6), 0, R, kStreamLead, p.k0, p.k1);
+      b = (pick(w, (i >> 4) & 3u) >> (2 * (i & 15u))) & 3u;
+    } else if (i < o0) {
+      b = bc[i - f5];
+    } else if (i >= o0 + p.oligo_len) {
+      b = bc[kSimMaxBarcode + i - o0 - p.oligo_len];
+    } else {
+      // lva_encode (Code::encode): the register at message step s is bits xb[s .. s + m], oldest first
+      const uint32_t info = posinfo[i - o0], s0 = info & 0xFFFu, T = info >> 12;
+      uint32_t reg0 = 0, reg1 = 0;
+      for (uint32_t a = 0; a <= m; ++a) {
+        reg0 |= (uint32_t)xb[s0 + a] << a;
+        reg1 |= (uint32_t)xb[s0 + 1 + a] << a;      // (xb is padded: s0 + 1 + m < kSimMaxBits)
+      }
+      uint32_t hi, lo;
+      if (T == 0) {
+        hi = __popc(reg0 & p.g0) & 1u;
+        lo = __popc(reg0 & p.g1) & 1u;
+      } else {                                      // two message bits: two of the four parity bits survive
+        hi = __popc(reg0 & ((T & 1u) ? p.g1 : p.g0)) & 1u;
+        lo = __popc(reg1 & (T == 1 ? p.g0 : p.g1)) & 1u;
+      }
+      b = 2 * hi + lo;
+    }
+    src[rc ? n - 1 - i : i] = (uint8_t)(rc ? 3u - b : b);
+  }
+  __syncthreads();
+
+  // ---- channel (stream 1): position i emits its insertions, then its own base unless deleted
+  int nb = 0;
+  for (uint32_t i0 = 0; i0 <= n; i0 += 64) {
+    const uint32_t i = i0 + (uint32_t)lane;
+    const U4 A = philox(i, 0, R, kStreamChannel, p.k0, p.k1), B = philox(i, 1, R, kStreamChannel, p.k0, p.k1);
+    int c = 0;
+    if (A.x < p.thr_ins) { c = 1; if (A.y < p.thr_ins) { c = 2; if (A.z < p.thr_ins) { c = 3; if (A.w < p.thr_ins) c = 4; } } }
+    const bool keep = i < n && !(B.y < p.thr_del);
+    const uint32_t s = i < n ? src[i] : 0u;
+    const uint32_t own = B.z < p.thr_sub ? (s + 1u + __umulhi(B.w, 3u)) & 3u : s;
+    const int e = i <= n ? c + (keep ? 1 : 0) : 0;
+    const int incl = wave_scan_add(e, lane);
+    int at = nb + incl - e;
+    if (i <= n) {
+      for (int k = 0; k < c; ++k) em[at++] = (uint8_t)((B.x >> (2 * k)) & 3u);
+      if (keep) em[at] = (uint8_t)own;
+    }
+    nb += __shfl(incl, 63, 64);
+  }
+  __syncthreads();
+
+  // ---- path and dwell (stream 2): states by synth.state_path's rule, one transition block and d stay blocks per base
+  const uint32_t lead = ((nb ? (uint32_t)em[0] : 0u) + 1u + __umulhi(L.x, 3u)) & 3u;
+  const int64_t row0 = fill ? row_off[r] : 0, base0 = fill ? base_off[r] : 0;
+  const int64_t rows = fill ? row_off[r + 1] - row0 : 0, nbase = fill ? base_off[r + 1] - base0 : 0;
+  int run_carry = 0, blocks = 0;
+  uint32_t st_carry = lead;
+  for (int j0 = 0; j0 < nb; j0 += 64) {
+    const int j = j0 + lane;
+    const bool act = j < nb;
+    const uint32_t b = act ? em[j] : 0u;
+    const bool start = act && (j == 0 || em[j - 1] != b);
+    const int run = max(wave_scan_max(start ? j : -1, lane), run_carry);      // where the run of equal bases began
+    const uint32_t st = b + 4u * (uint32_t)((j - run) & 1);
+    uint32_t prev = __shfl_up(st, 1, 64);
+    if (lane == 0) prev = st_carry;
+    run_carry = __shfl(run, 63, 64);
+    st_carry = __shfl(st, 63, 64);
+    const U4 w4 = philox((uint32_t)j >> 2, 0, R, kStreamDwell, p.k0, p.k1);
+    const uint32_t w = pick(w4, (uint32_t)j & 3u);
+    int d = (int)p.dwell_k;
+    for (int e = (int)p.dwell_k - 1; e >= 0; --e)
+      if (w < s_cdf[e]) d = e;
+    const int mine = act ? 1 + d : 0;
+    const int incl = wave_scan_add(mine, lane);
+    const int64_t at = 1 + blocks + incl - mine;              // the block of this base's transition
+    if (fill && act) {
+      if (j < nbase) bases[base0 + j] = (uint8_t)b;
+      if (at < rows) true_idx[row0 + at] = (uint8_t)transition_index(prev, st);
+      const uint8_t stay = (uint8_t)transition_index(st, st);
+      for (int q = 1; q <= d; ++q)
+        if (at + q < rows) true_idx[row0 + at + q] = stay;
+    }
+    blocks += __shfl(incl, 63, 64);
+  }
+  if (lane == 0) {
+    if (!fill) {
+      lens[2 * r] = nb;
+      lens[2 * r + 1] = 1 + blocks;
+    } else {
+      if (rows > 0) true_idx[row0] = (uint8_t)(lead * 9u);     // one leading stay block
+      if (nbase != nb || rows != 1 + blocks) *bad = 1;
+    }
+  }
+}
+
+// Flat over the batch's 16-byte quads (10 per block): a lane draws two Philox calls and stores one quad, a wavefront's stores
+// are 1 KiB in a row.  The read of a wavefront's first block comes from one search per wavefront; lanes step on from it.
+__global__ __launch_bounds__(256) void sim_scores(uint32_t k0, uint32_t k1, uint32_t first_read, int32_t n_reads,
+                                                  const int64_t* __restrict__ row_off, uint32_t quads,
+                                                  const uint8_t* __restrict__ true_idx, float scale, float margin, float clip,
+                                                  float* __restrict__ scores) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t stride = gridDim.x * 256u;
+  for (uint64_t g64 = (uint64_t)blockIdx.x * 256u + (threadIdx.x & ~63u); g64 < quads; g64 += stride) {
+    const uint32_t wave0 = __builtin_amdgcn_readfirstlane((uint32_t)g64);
+    const int64_t blk0 = wave0 / 10u;
+    int lo = 0, hi = n_reads - 1;                  // the last read that begins at or before blk0
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (row_off[mid] <= blk0) lo = mid; else hi = mid - 1;
+    }
+    const uint64_t g = (uint64_t)wave0 + lane;
+    if (g >= quads) continue;
+    const uint32_t blk = (uint32_t)g / 10u, q = (uint32_t)g - blk * 10u;
+    int r = lo;
+    while (row_off[r + 1] <= (int64_t)blk) ++r;    // blk < row_off[n_reads]: ends at the latest at n_reads - 1
+    const uint32_t t = blk - (uint32_t)row_off[r], R = first_read + (uint32_t)r;
+    const U4 a = philox(t, 2 * q, R, kStreamNoise, k0, k1), b = philox(t, 2 * q + 1, R, kStreamNoise, k0, k1);
+    const uint32_t ti = true_idx[blk];
+    const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    float v[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const uint32_t x = w[2 * e], y = w[2 * e + 1];
+      const int s = (int)((x & 0xFFFFu) + (x >> 16) + (y & 0xFFFFu) + (y >> 16)) - 131070;
+      float f = (float)s * scale;
+      if (4 * q + (uint32_t)e == ti) f = f + margin;
+      v[e] = fminf(fmaxf(f, -clip), clip);
+    }
+    *reinterpret_cast<float4*>(scores + (size_t)g * 4) = make_float4(v[0], v[1], v[2], v[3]);
+  }
+}
+
+}  // namespace
+
+int launch_sim_strand(const SimParams& p, int32_t n_reads, const uint16_t* posinfo, const uint32_t* cdf, const uint8_t* bc,
+                      const int64_t* row_off, const int64_t* base_off, int32_t* lens, uint8_t* msgs, uint8_t* bases,
+                      uint8_t* true_idx, int32_t* bad, void* stream) {
+  if (n_reads <= 0) return 0;
+  hipLaunchKernelGGL(sim_strand, dim3((uint32_t)n_reads), dim3(64), 0, (hipStream_t)stream, p, posinfo, cdf, bc, row_off, base_off,
+                     lens, msgs, bases, true_idx, bad);
+  return (int)hipGetLastError();
+}
+
+int launch_sim_scores(const SimParams& p, int32_t n_reads, const int64_t* row_off, uint32_t blocks, const uint8_t* true_idx,
+                      float scale, float margin, float clip, float* scores, void* stream) {
+  if (n_reads <= 0 || blocks == 0) return 0;
+  const uint32_t quads = blocks * 10u;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)quads + 255) / 256, 2048);
+  hipLaunchKernelGGL(sim_scores, dim3(grid), dim3(256), 0, (hipStream_t)stream, p.k0, p.k1, p.first_read, n_reads, row_off, quads,
+                     true_idx, scale, margin, clip, scores);
+  return (int)hipGetLastError();
+}
+
+}  // namespace lva

@@ -446,6 +446,44 @@ class Decoder:
             self.posteriors_resident(ctypes.c_void_p(scores.data_ptr()), off, out_ptr=dev)
             return self._decode_chain_resident(dev, off, rc, start_barcode, end_barcode)
 
+    # --- reads made on the device (simulate.py is the definition) ----------------
+    @contextmanager
+    def simulate(self, n, seed, first_read=0, **kw):
+        """n simulated reads of this decoder's code, numbers first_read .. first_read + n - 1 under `seed`, as transition
+        scores in HBM for the length of a `with` block -> (device pointer, row_offsets, truth); truth: dict(msgs uint8
+        [n, msg_len], bases uint8, base_offsets int64 [n + 1], true_idx uint8 [blocks]).  Keywords (simulate.parameters): sub,
+        dele, ins, margin, sigma, clip, dwell_cdf, start_barcode, end_barcode, flank, rc_mode.  Bit for bit what
+        simulate.reference_reads gives for the same arguments; a read depends on (seed, read number) alone."""
+        from . import simulate as sim
+        q = sim.parameters(**kw)
+        if n < 0 or first_read < 0 or first_read + n > 1 << 32:
+            raise ValueError("read numbers are 32-bit")
+        cdf = q["cdf"]
+        bc = [None if b is None else b.encode() for b in (q["start_barcode"], q["end_barcode"])]
+        shared = (self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_read), int(n), q["sub"], q["dele"], q["ins"], cdf.ctypes.data,
+                  len(cdf), bc[0], bc[1], q["flank"][0], q["flank"][1], q["rc_mode"])
+        row, base = np.zeros(max(n, 0) + 1, np.int64), np.zeros(max(n, 0) + 1, np.int64)
+        self._check(self._L.lva_simulate_plan(*shared, row.ctypes.data, base.ctypes.data))
+        msgs = np.zeros((n, self.msg_len), np.uint8)
+        bases, true_idx = np.zeros(max(int(base[-1]), 1), np.uint8), np.zeros(max(int(row[-1]), 1), np.uint8)
+        with self.resident(max(int(row[-1]), 1) * 160) as (dev, _):
+            self._check(self._L.lva_simulate_fill_device(*shared, float(q["scale"]), float(q["margin"]), float(q["clip"]),
+                                                         row.ctypes.data, base.ctypes.data, dev, msgs.ctypes.data,
+                                                         bases.ctypes.data, true_idx.ctypes.data))
+            yield dev, row, dict(msgs=msgs, bases=bases[:int(base[-1])], base_offsets=base, true_idx=true_idx[:int(row[-1])])
+
+    def simulate_and_decode(self, n, seed, first_read=0, **kw):
+        """simulate -> posteriors in place -> decode (with both barcodes: locate_payload_resident -> decode_located) without
+        the scores leaving the device -> (truth, results); results as decode() / decode_with_barcodes() give them.  Without
+        barcodes the orientation of every read is passed to the decoder as the simulator chose it (rc_mode)."""
+        with self.simulate(n, seed, first_read, **kw) as (dev, off, truth):
+            self.posteriors_resident(dev, off)
+            if kw.get("start_barcode") is not None:
+                return truth, self._decode_chain_resident(dev, off, None, kw["start_barcode"], kw["end_barcode"])
+            mode = kw.get("rc_mode", 0)
+            rc = [mode == 1 or (mode == 2 and bool((first_read + i) & 1)) for i in range(n)]
+            return truth, self.decode_resident(dev, off, rc)
+
     # --- decode stream: reads go in one at a time, results come out as they finish -------------
     def stream(self, queue_cap=None):
         """A DecodeStream on this decoder (a context manager).  queue_cap: reads that may wait for a slot before submit()

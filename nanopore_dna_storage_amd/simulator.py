@@ -13,7 +13,7 @@ import sys
 import numpy as np
 
 from . import helper, synth
-from .decoder import Decoder, bases_to_str
+from .decoder import Decoder, bases_to_str, encode
 
 
 def build_parser():
@@ -34,6 +34,9 @@ def build_parser():
     p.add_argument("--margin", type=float, default=6.0)
     p.add_argument("--max_deviation", type=int, default=20)
     p.add_argument("--device", type=int, default=0)
+    p.add_argument("--synth", choices=["host", "device"], default="host",
+                   help="where the reads are made: synth.py on the host, or the counter-based simulator on the GPU "
+                        "(Decoder.simulate: the reference's insertion / deletion / substitution rules, transition scores)")
     p.add_argument("--stats", choices=["host", "device"], default="host",
                    help="where the per-trial statistics are computed: Python loops, or the GPU (list_ops.list_stats); same output")
     return p
@@ -41,18 +44,32 @@ def build_parser():
 
 def run(args, out=sys.stdout, decoder=None):
     revcomp = args.reversecomp != "False"
-    reads = [synth.make_read(args.mem_conv, args.rate, args.msg_len, args.seed + i, rc=revcomp,
-                             margin=args.margin, sub=args.syn_sub_prob, dele=args.syn_del_prob,
-                             ins=args.syn_ins_prob) for i in range(args.num_trials)]
+    on_device = getattr(args, "synth", "host") == "device"
+    if not on_device:
+        reads = [synth.make_read(args.mem_conv, args.rate, args.msg_len, args.seed + i, rc=revcomp,
+                                 margin=args.margin, sub=args.syn_sub_prob, dele=args.syn_del_prob,
+                                 ins=args.syn_ins_prob) for i in range(args.num_trials)]
     own = decoder is None
     if own:
         decoder = Decoder(args.mem_conv, args.rate, args.msg_len, list_size=args.list_size,
                           max_deviation=args.max_deviation, device=args.device)
     try:
-        results = decoder.decode([r["post"] for r in reads], rc=[revcomp] * len(reads))
+        if on_device:      # reads made, turned into posteriors and decoded on the device: the truth is all that comes back
+            truth, results = decoder.simulate_and_decode(args.num_trials, args.seed, margin=args.margin, sub=args.syn_sub_prob,
+                                                         dele=args.syn_del_prob, ins=args.syn_ins_prob, rc_mode=int(revcomp))
+            oligos = encode(args.mem_conv, args.rate, args.msg_len, truth["msgs"]) if args.num_trials else []
+            reads = [dict(msg=m, oligo=o) for m, o in zip(truth["msgs"], oligos)]
+        else:
+            results = decoder.decode([r["post"] for r in reads], rc=[revcomp] * len(reads))
     finally:
         if own:
             decoder.close()
+    return report(args, reads, results, out)
+
+
+def report(args, reads, results, out=sys.stdout):
+    """The per-trial and summary statistics (simulator.py:92-126) of decoded reads: reads = dicts with msg and oligo, results
+    = what Decoder.decode returns for them.  Prints the reference's text to `out` -> the summary statistics."""
     top, lst, ham, ham8, ham16, edit = [], [], [], [], [], []
     n = args.msg_len
     dev = None
