@@ -464,6 +464,31 @@ int lva_list_stats(int32_t device, const uint8_t *msgs, const int32_t *counts, c
                    int32_t list_size, uint32_t msg_len, lva_list_stat *out);
 
 /* ---------------------------------------------------------------------------------------------
+ * DESIGN.md section 1 row N4': reading-cost trials -- the loop of decode_RS_from_decoded_lists.py:30-66 (draw a sample of
+ * the reads, vote per index, RS-decode, compare with the original file) for n_trials trials and n_points sample sizes
+ * in one call.  Which reads trial t draws, and in which order, is defined by a keyed permutation of the read numbers
+ * (nanopore_dna_storage_amd/trials.py: Feistel network over Philox4x32-10, stream 5, with cycle walking; the sample of size
+ * u is its first u reads, so the samples of one trial are nested); a trial depends on (seed, trial number) alone.
+ *   index [n_reads], payload [n_reads][bytes_per_oligo]: lva_list_filter's outputs for ALL read numbers (a read without a
+ *                  list: index -1); an index >= num_oligos is LVA_ERR_ARG;
+ *   bytes_per_oligo even and >= 2; 1 <= num_oligos <= 4096; 1 <= redundancy <= min(4096, num_oligos - 1);
+ *   original       the file, 1 <= original_bytes <= (num_oligos - redundancy) * bytes_per_oligo;
+ *   reads_to_use   [n_points] ascending sample sizes in [0, n_reads], 1 <= n_points <= 64;
+ *   trials first_trial .. first_trial + n_trials - 1 (32-bit trial numbers), chunk_trials of them at a time on the
+ *                  device (0, or more than fit: as many as fit 1 GiB); the result does not depend on it;
+ *   out_stats      [n_points][n_trials] x (passed: reads of the sample that carry an index; present: indices with a vote;
+ *                  columns_ok: columns the decoder did not give up on, 0 when present is 0; success: present > 0 and the
+ *                  decoded data begin with the original file);
+ *   out_present, out_payload (each may be NULL): the vote's result, as lva_list_consensus lays it out, per point and trial.
+ * Takes a device ordinal like the lva_list_* calls and behaves like them; n_trials = 0 or n_reads = 0 succeeds and
+ * touches nothing.
+ * ------------------------------------------------------------------------------------------- */
+int lva_rs_trials(int32_t device, const int32_t *index, const uint8_t *payload, int32_t n_reads, int32_t bytes_per_oligo,
+                  int32_t num_oligos, int32_t redundancy, const uint8_t *original, int64_t original_bytes,
+                  const int32_t *reads_to_use, int32_t n_points, uint64_t seed, uint32_t first_trial, int32_t n_trials,
+                  int32_t chunk_trials, int32_t *out_stats, uint8_t *out_present, uint8_t *out_payload);
+
+/* ---------------------------------------------------------------------------------------------
  * reads made on the device, in front of lva_transpost_batch_device -- random message ->
  * lva_encode's oligo of the decoder's (mem_conv, rate, msg_len) -> strand -> insertion / deletion / substitution channel
  * -> flip-flop path and dwells -> transition scores in the layout above.  Every draw is a word of Philox4x32-10 under

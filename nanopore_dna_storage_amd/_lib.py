@@ -137,6 +137,7 @@ ABI = {
     "lva_list_filter": (_int, [_i32, _vp, _vp, _i32, _i32, _u32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "lva_list_consensus": (_int, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "lva_list_stats": (_int, [_i32, _vp, _vp, _vp, _i32, _i32, _u32, _vp]),
+    "lva_rs_trials": (_int, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, ctypes.c_int64, _vp, _i32, _u64, _u32, _i32, _i32, _vp, _vp, _vp]),
     "lva_simulate_plan": (_int, _sim + [_vp, _vp]),
     "lva_simulate_fill_device": (_int, _sim + [_f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }

@@ -27,6 +27,9 @@ int launch_ls_filter(const uint8_t* msgs, const int32_t* counts, int32_t n_reads
 int launch_ls_consensus(const int32_t* index, const uint8_t* payload, int32_t n_reads, int32_t bytes_per_oligo,
                         int32_t num_oligos, int32_t first_only, int32_t* bucket, int32_t* order, uint8_t* present,
                         uint8_t* out_payload, int32_t* votes, void* stream);
+// The first two launches of the consensus alone, for a consumer of its own (tr_kernels.hip): bucket [num_oligos + 1] =
+// where the reads of every index begin in a list of the reads index by index (members per index, then prefix sums).
+int launch_ls_bucket_scan(const int32_t* index, int32_t n_reads, int32_t num_oligos, int32_t* bucket, void* stream);
 // truth [n_reads][msg_len]; packed [n_reads][kLsPackWords] uint64 scratch; out [n_reads][kLsStatFields] int32:
 // top_correct, list_correct, hamming, hamming8, hamming16, edit (all -1 for a read without a list).
 // Two launches: one wavefront per read for everything but the edit distance, then one thread per read for it.

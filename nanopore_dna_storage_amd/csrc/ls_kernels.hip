@@ -18,6 +18,7 @@
 #include <climits>
 #include <cstdint>
 
+#include "ls_bucket.h"
 #include "ls_kernels.h"
 
 namespace lva {
@@ -150,15 +151,7 @@ __global__ __launch_bounds__(64) void ls_consensus(const int32_t* __restrict__ i
     return;
   }
   int32_t* mem = order + s;
-  int pos = 0;
-  for (int i0 = 0; i0 < n_reads && pos < t; i0 += 64) {
-    const int i = i0 + lane;
-    const bool m = i < n_reads && index[i] == x;
-    const unsigned long long mask = __ballot(m);
-    const int at = pos + __popcll(mask & ((1ull << lane) - 1ull));
-    if (m && at < t) mem[at] = i;
-    pos += __popcll(mask);
-  }
+  list_bucket(index, n_reads, x, t, mem, lane);
   __syncthreads();                                       // the list is read back by other lanes
   int best_c = 0, best_j = INT_MAX;
   if (first_only) {
@@ -325,6 +318,14 @@ int launch_ls_consensus(const int32_t* index, const uint8_t* payload, int32_t n_
   hipLaunchKernelGGL(ls_bucket_scan, dim3(1), dim3(256), 0, st, bucket, num_oligos);
   hipLaunchKernelGGL(ls_consensus, dim3(num_oligos), dim3(64), 0, st, index, payload, n_reads, bytes_per_oligo, first_only, bucket,
                      order, present, out_payload, votes);
+  return (int)hipGetLastError();
+}
+
+int launch_ls_bucket_scan(const int32_t* index, int32_t n_reads, int32_t num_oligos, int32_t* bucket, void* stream) {
+  if (n_reads <= 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(ls_bucket_count, dim3(num_oligos), dim3(64), 0, st, index, n_reads, bucket);
+  hipLaunchKernelGGL(ls_bucket_scan, dim3(1), dim3(256), 0, st, bucket, num_oligos);
   return (int)hipGetLastError();
 }
 

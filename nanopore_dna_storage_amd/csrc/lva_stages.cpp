@@ -1,5 +1,5 @@
 // lva_stages.cpp -- C ABI (include/lva_decoder.h) of the stages beside the list decoder: transition posteriors (N0), basecall
-// and barcode localisation (N3), demultiplexing (N3'), the consumers of a decoded list (N2).  No algorithm lives here: an entry
+// and barcode localisation (N3), demultiplexing (N3'), the consumers of a decoded list (N2), reading-cost trials (N4'), the read simulator (S).  No algorithm lives here: an entry
 // point checks its arguments, declares its device pieces, uploads, launches, copies back and waits, all through the functions below.
 #include <algorithm>
 #include <cstring>
@@ -9,6 +9,7 @@
 #include "tp_kernels.h"
 #include "ls_kernels.h"
 #include "sim_kernels.h"
+#include "tr_kernels.h"
 
 using namespace lva;
 
@@ -548,6 +549,112 @@ int lva_list_stats(int32_t device, const uint8_t* msgs, const int32_t* counts, c
                                 arena.ptr(d_packed), arena.ptr(d_out), st.s);
   if (e) return launch_status(e);
   HIP_TRY(hipMemcpyAsync(out, arena.ptr(d_out), 4 * kLsStatFields * n, hipMemcpyDeviceToHost, st.s));
+  return drain.finish();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// DESIGN.md section 1 row N4': reading-cost trials (csrc/tr_kernels.hip; the definition is trials.py).  Like the list
+// consumers: a device ordinal, a stream of its own, complete on return.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+constexpr size_t kTrChunkBytes = (size_t)1 << 30;        // what a chunk of trials may occupy on the device
+
+// everything lva_rs_trials can refuse without the device
+int trials_args(const int32_t* index, const uint8_t* payload, int32_t n_reads, int32_t bpo, int32_t num_oligos, int32_t redundancy,
+                const uint8_t* original, int64_t original_bytes, const int32_t* reads_to_use, int32_t n_points,
+                uint32_t first_trial, int32_t n_trials, int32_t chunk_trials, const int32_t* out_stats) {
+  if (n_reads < 0 || n_trials < 0 || chunk_trials < 0) return LVA_ERR_ARG;
+  if (bpo < 2 || (bpo & 1) || num_oligos < 1 || num_oligos > 4096) return LVA_ERR_ARG;
+  if (redundancy < 1 || redundancy > std::min(4096, num_oligos - 1)) return LVA_ERR_ARG;
+  if (n_points < 1 || n_points > kTrMaxPoints || !reads_to_use) return LVA_ERR_ARG;
+  if (!original || original_bytes < 1 || original_bytes > (int64_t)(num_oligos - redundancy) * bpo) return LVA_ERR_ARG;
+  if ((uint64_t)first_trial + (uint64_t)n_trials > ((uint64_t)1 << 32)) return LVA_ERR_ARG;      // trial numbers are 32-bit
+  if ((n_reads > 0 && (!index || !payload)) || (n_trials > 0 && !out_stats)) return LVA_ERR_ARG;
+  if ((uint64_t)n_reads * (uint64_t)bpo >= (1ull << 31)) return LVA_ERR_ARG;
+  for (int32_t k = 0; k < n_points; ++k)
+    if (reads_to_use[k] < 0 || reads_to_use[k] > n_reads || (k > 0 && reads_to_use[k] < reads_to_use[k - 1])) return LVA_ERR_ARG;
+  for (int32_t i = 0; i < n_reads; ++i)
+    if (index[i] >= num_oligos) return LVA_ERR_ARG;      // (negative: the read passed no entry and has no vote)
+  return LVA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lva_rs_trials(int32_t device, const int32_t* index, const uint8_t* payload, int32_t n_reads, int32_t bytes_per_oligo,
+                  int32_t num_oligos, int32_t redundancy, const uint8_t* original, int64_t original_bytes,
+                  const int32_t* reads_to_use, int32_t n_points, uint64_t seed, uint32_t first_trial, int32_t n_trials,
+                  int32_t chunk_trials, int32_t* out_stats, uint8_t* out_present, uint8_t* out_payload) {
+  if (trials_args(index, payload, n_reads, bytes_per_oligo, num_oligos, redundancy, original, original_bytes, reads_to_use, n_points,
+                  first_trial, n_trials, chunk_trials, out_stats) != LVA_OK)
+    return LVA_ERR_ARG;
+  if (n_trials == 0 || n_reads == 0) return LVA_OK;
+  const size_t n = (size_t)n_reads, no = (size_t)num_oligos, bpo = (size_t)bytes_per_oligo, s = bpo / 2, K = (size_t)n_points;
+  const size_t nd = no - (size_t)redundancy, T = (size_t)n_trials;
+  // bytes of one trial in a chunk: RS input and output, members and erasures per index, the places and counts of the reads
+  const size_t per_trial = K * (2 * s * no + 2 * s * nd + 8 * no + 8 * s + 12 + (out_payload ? no * bpo : 0) + (out_present ? no : 0)) + 8 * n;
+  size_t chunk = std::min(T, std::max<size_t>(kTrChunkBytes / per_trial, 1));
+  if (chunk_trials > 0) chunk = std::min(chunk, (size_t)chunk_trials);
+  TrShape sh{};
+  sh.n_reads = n_reads; sh.bpo = bytes_per_oligo; sh.num_oligos = num_oligos; sh.fec = redundancy; sh.n_points = n_points;
+  sh.k0 = (uint32_t)seed; sh.k1 = (uint32_t)(seed >> 32);
+  std::copy(reads_to_use, reads_to_use + n_points, sh.points);
+  std::vector<uint16_t> gexp, glog, truth(s * nd, 0);    // (these outlive the call's StreamDrain)
+  tr_gf_tables(&gexp, &glog);
+  for (size_t c = 0; c < s; ++c)                         // column c of the original file, as the decoder's output is laid out
+    for (size_t j = 0; j < nd; ++j) {
+      const int64_t at = (int64_t)(j * bpo + 2 * c);
+      const uint32_t lo = at < original_bytes ? original[at] : 0u, hi = at + 1 < original_bytes ? original[at + 1] : 0u;
+      truth[c * nd + j] = (uint16_t)(lo | (hi << 8));
+    }
+  LsStream st;
+  if (const int so = ls_open(device, &st)) return so;
+  Arena arena;
+  const auto d_index = arena.add<int32_t>(n), d_order = arena.add<int32_t>(n);
+  const auto d_pay = arena.add<uint8_t>(n * bpo);
+  const auto d_bucket = arena.add<int32_t>(no + 1);
+  const auto d_gexp = arena.add<uint16_t>(kTrGexpWords), d_glog = arena.add<uint16_t>(kTrGlogWords), d_truth = arena.add<uint16_t>(s * nd);
+  const auto d_stats = arena.add<int32_t>(4 * K * T);
+  const auto d_place = arena.add<int32_t>(chunk * n), d_cnt = arena.add<int32_t>(chunk * n);
+  const auto d_nmem = arena.add<int32_t>(K * chunk * no), d_erl = arena.add<int32_t>(K * chunk * no);
+  const auto d_ern = arena.add<int32_t>(K * chunk), d_pp = arena.add<int32_t>(2 * K * chunk), d_okeq = arena.add<int32_t>(2 * K * chunk * s);
+  const auto d_sym = arena.add<uint16_t>(K * chunk * s * no), d_dec = arena.add<uint16_t>(K * chunk * s * nd);
+  const auto d_cons = out_payload ? arena.add<uint8_t>(K * chunk * no * bpo) : Arena::Piece<uint8_t>{};
+  const auto d_pres = out_present ? arena.add<uint8_t>(K * chunk * no) : Arena::Piece<uint8_t>{};
+  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
+  StreamDrain drain(st.s);
+  HIP_TRY(hipMemcpyAsync(arena.ptr(d_index), index, 4 * n, hipMemcpyHostToDevice, st.s));
+  HIP_TRY(hipMemcpyAsync(arena.ptr(d_pay), payload, n * bpo, hipMemcpyHostToDevice, st.s));
+  HIP_TRY(hipMemcpyAsync(arena.ptr(d_gexp), gexp.data(), 2 * kTrGexpWords, hipMemcpyHostToDevice, st.s));
+  HIP_TRY(hipMemcpyAsync(arena.ptr(d_glog), glog.data(), 2 * kTrGlogWords, hipMemcpyHostToDevice, st.s));
+  HIP_TRY(hipMemcpyAsync(arena.ptr(d_truth), truth.data(), 2 * s * nd, hipMemcpyHostToDevice, st.s));
+  int e = launch_ls_bucket_scan(arena.ptr(d_index), n_reads, num_oligos, arena.ptr(d_bucket), st.s);
+  if (!e) e = launch_tr_bucket_list(arena.ptr(d_index), n_reads, num_oligos, arena.ptr(d_bucket), arena.ptr(d_order), st.s);
+  if (e) return launch_status(e);
+  for (size_t at = 0; at < T; at += chunk) {             // a trial depends on (seed, trial number) alone: chunks change nothing
+    const size_t c = std::min(chunk, T - at);
+    sh.chunk = (int32_t)c;
+    sh.first_trial = first_trial + (uint32_t)at;
+    e = launch_tr_consensus(sh, arena.ptr(d_bucket), arena.ptr(d_order), arena.ptr(d_pay), arena.ptr(d_place), arena.ptr(d_cnt),
+                            arena.ptr(d_nmem), arena.ptr(d_sym), arena.ptr(d_cons), st.s);
+    if (!e) e = launch_tr_erasures(sh, arena.ptr(d_nmem), arena.ptr(d_erl), arena.ptr(d_ern), arena.ptr(d_pp), arena.ptr(d_pres), st.s);
+    if (!e) e = launch_tr_decode(sh, arena.ptr(d_sym), arena.ptr(d_erl), arena.ptr(d_ern), arena.ptr(d_gexp), arena.ptr(d_glog),
+                                 arena.ptr(d_dec), arena.ptr(d_truth), original_bytes, arena.ptr(d_okeq), st.s);
+    if (!e) e = launch_tr_fold(sh, arena.ptr(d_okeq), arena.ptr(d_pp), arena.ptr(d_stats), n_trials, (int32_t)at, st.s);
+    if (e) return launch_status(e);
+    for (size_t k = 0; k < K; ++k) {                     // the chunk holds [point][trial of the chunk], the caller [point][trial]
+      if (out_present)
+        HIP_TRY(hipMemcpyAsync(out_present + (k * T + at) * no, arena.ptr(d_pres) + k * c * no, c * no, hipMemcpyDeviceToHost, st.s));
+      if (out_payload)
+        HIP_TRY(hipMemcpyAsync(out_payload + (k * T + at) * no * bpo, arena.ptr(d_cons) + k * c * no * bpo, c * no * bpo,
+                               hipMemcpyDeviceToHost, st.s));
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(out_stats, arena.ptr(d_stats), 16 * K * T, hipMemcpyDeviceToHost, st.s));
   return drain.finish();
 }
 

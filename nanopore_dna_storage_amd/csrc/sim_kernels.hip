@@ -7,28 +7,15 @@
 
 #include <algorithm>
 
+#include "philox.h"
 #include "sim_kernels.h"
 
 namespace lva {
 
 namespace {
 
-constexpr uint32_t kM0 = 0xD2511F53u, kM1 = 0xCD9E8D57u, kW0 = 0x9E3779B9u, kW1 = 0xBB67AE85u;
-constexpr uint32_t kStreamMessage = 0, kStreamChannel = 1, kStreamDwell = 2, kStreamNoise = 3, kStreamLead = 4;
 constexpr int kSimMaxEmit = 5 * kSimMaxStrand + 4;     // 4 insertions + the base per position, 4 more behind the last
 constexpr int kSimMaxBits = 544;                       // mem_conv initial bits + message + termination (2 * 255 + 14 at most)
-
-struct U4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ U4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t h0 = __umulhi(kM0, c0), l0 = kM0 * c0, h1 = __umulhi(kM1, c2), l1 = kM1 * c2;
-    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-    k0 += kW0; k1 += kW1;
-  }
-  return {c0, c1, c2, c3};
-}
 
 __device__ __forceinline__ uint32_t pick(const U4& v, uint32_t i) {      // v[i] without an indexed register array
   return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w;
