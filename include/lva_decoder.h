@@ -528,6 +528,31 @@ int lva_simulate_fill_device(lva_decoder *d, uint64_t seed, uint32_t first_read,
                              const int64_t *base_offsets, float *scores_dev, uint8_t *msgs_out, uint8_t *bases_out,
                              uint8_t *true_idx_out);
 
+/* The same pair with a pool source: the message of read number k is not drawn bit by bit but is one of n_pool given
+ * messages -- the oligos of an encoded file -- chosen by k under the seed (stream 6 of simulate.py: counter (0, 0, k, 6),
+ * words w0..w3).  Every other draw of the read is what the pair above makes of the same arguments.
+ *   pool [n_pool][msg_len]   host, bytes 0 / 1; 1 <= n_pool <= 2^24 and n_pool * msg_len < 2^31; uploaded per call;
+ *   pool_cdf [n_pool]        host, or NULL: entry mulhi(w0, n_pool).  Given: non-decreasing, last entry 0xFFFFFFFF; the
+ *                            entry is the first k with w0 < pool_cdf[k], else n_pool - 1, so an entry equal to its
+ *                            predecessor is never drawn (uneven coverage: simulate.weights_to_cdf);
+ *   rc_mode                  0, 1, 2 as above, 3: the strand is reverse-complemented iff w1 >> 31.
+ * A NULL pool, an n_pool outside its range, a pool byte above 1 or a table that decreases or does not end in 0xFFFFFFFF is
+ * LVA_ERR_ARG, one of the call's own arguments in the refusal order above (before LVA_ERR_UNSUPPORTED for a sync marker).
+ * The fill call also reports what was drawn: source_out int32 [n_reads] (the pool entry) and rc_out uint8 [n_reads] (1: the
+ * strand was reverse-complemented), either may be NULL; msgs_out [i] = pool [source_out [i]]. */
+int lva_simulate_pool_plan(lva_decoder *d, uint64_t seed, uint32_t first_read, int32_t n_reads, uint32_t sub_thr,
+                           uint32_t del_thr, uint32_t ins_thr, const uint32_t *dwell_cdf, int32_t dwell_k,
+                           const char *start_barcode, const char *end_barcode, uint32_t flank_lo, uint32_t flank_hi,
+                           int32_t rc_mode, const uint8_t *pool, int32_t n_pool, const uint32_t *pool_cdf,
+                           int64_t *row_offsets_out, int64_t *base_offsets_out);
+int lva_simulate_pool_fill_device(lva_decoder *d, uint64_t seed, uint32_t first_read, int32_t n_reads, uint32_t sub_thr,
+                                  uint32_t del_thr, uint32_t ins_thr, const uint32_t *dwell_cdf, int32_t dwell_k,
+                                  const char *start_barcode, const char *end_barcode, uint32_t flank_lo, uint32_t flank_hi,
+                                  int32_t rc_mode, const uint8_t *pool, int32_t n_pool, const uint32_t *pool_cdf, float scale,
+                                  float margin, float clip, const int64_t *row_offsets, const int64_t *base_offsets,
+                                  float *scores_dev, uint8_t *msgs_out, uint8_t *bases_out, uint8_t *true_idx_out,
+                                  int32_t *source_out, uint8_t *rc_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -90,6 +90,7 @@ _demux = [_vp, _i32, _i32, _i32, _vp, _vp]           # exps, n_exps, max_dist, m
 _f32 = ctypes.c_float
 # d, seed, first_read, n_reads, sub / del / ins thresholds, dwell_cdf, dwell_k, barcodes, flank_lo, flank_hi, rc_mode
 _sim = [_vp, _u64, _u32, _i32, _u32, _u32, _u32, _vp, _i32, _cp, _cp, _u32, _u32, _i32]
+_pool = [_vp, _i32, _vp]         # pool, n_pool, pool_cdf
 
 # The C ABI, once: every function include/lva_decoder.h declares -> (restype, argtypes), in the header's order
 # (tests/test_abi_table_host.py parses the header and holds this table and the structures above to it)
@@ -140,6 +141,8 @@ ABI = {
     "lva_rs_trials": (_int, [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, ctypes.c_int64, _vp, _i32, _u64, _u32, _i32, _i32, _vp, _vp, _vp]),
     "lva_simulate_plan": (_int, _sim + [_vp, _vp]),
     "lva_simulate_fill_device": (_int, _sim + [_f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lva_simulate_pool_plan": (_int, _sim + _pool + [_vp, _vp]),
+    "lva_simulate_pool_fill_device": (_int, _sim + _pool + [_f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTS = list(ABI)
 

@@ -673,12 +673,33 @@ struct SimCall {
   uint8_t bc[2 * kSimMaxBarcode] = {0};   // start barcode, end barcode as 0..3
 };
 
-// a call's own arguments, the barcodes apart: everything both entry points share
+// The pool of the lva_simulate_pool_* pair, as the caller gave it; the other pair passes none.
+struct SimPoolHost {
+  const uint8_t* msgs;
+  int32_t n;
+  const uint32_t* cdf;
+};
+
+bool sim_pool_ok(const SimPoolHost& pool, uint32_t msg_len) {
+  if (!pool.msgs || pool.n < 1 || pool.n > kSimMaxPool || (uint64_t)pool.n * msg_len >= ((uint64_t)1 << 31)) return false;
+  const size_t bytes = (size_t)pool.n * msg_len;
+  for (size_t i = 0; i < bytes; ++i)
+    if (pool.msgs[i] > 1) return false;
+  if (pool.cdf) {
+    for (int32_t k = 1; k < pool.n; ++k)
+      if (pool.cdf[k] < pool.cdf[k - 1]) return false;
+    if (pool.cdf[pool.n - 1] != 0xFFFFFFFFu) return false;
+  }
+  return true;
+}
+
+// a call's own arguments, the barcodes apart: everything the entry points share.  pool: null, or what rc_mode 3 needs
 int sim_args(lva_decoder* d, uint64_t seed, uint32_t first_read, int32_t n, uint32_t sub_thr, uint32_t del_thr, uint32_t ins_thr,
-             const uint32_t* dwell_cdf, int32_t dwell_k, int32_t rc_mode, SimCall* c) {
-  if (!d || n < 0 || !dwell_cdf || dwell_k < 1 || dwell_k > kSimMaxDwell || rc_mode < 0 || rc_mode > 2) return LVA_ERR_ARG;
+             const uint32_t* dwell_cdf, int32_t dwell_k, int32_t rc_mode, const SimPoolHost* pool, SimCall* c) {
+  if (!d || n < 0 || !dwell_cdf || dwell_k < 1 || dwell_k > kSimMaxDwell || rc_mode < 0 || rc_mode > (pool ? 3 : 2)) return LVA_ERR_ARG;
   if ((uint64_t)first_read + (uint64_t)n > ((uint64_t)1 << 32)) return LVA_ERR_ARG;        // read numbers are 32-bit
   if (sub_thr > kSimMaxThreshold || del_thr > kSimMaxThreshold || ins_thr > kSimMaxThreshold) return LVA_ERR_ARG;
+  if (pool && !sim_pool_ok(*pool, d->code[0].msg_len)) return LVA_ERR_ARG;
   if (!d->sync_marker.empty()) return LVA_ERR_UNSUPPORTED;                                 // lva_encode takes no marker
   const Code& code = d->code[0];
   SimParams& p = c->p;
@@ -724,28 +745,45 @@ struct SimTables {
   Arena::Piece<uint16_t> posinfo;
   Arena::Piece<uint32_t> cdf;
   Arena::Piece<uint8_t> bc;
+  Arena::Piece<uint8_t> pool;             // with a pool only: its messages, its table if it has one, and per read what was drawn
+  Arena::Piece<uint32_t> pool_cdf;
+  Arena::Piece<int32_t> source;
+  Arena::Piece<uint8_t> rc;
 };
-SimTables sim_tables(Arena& a, const SimCall& c) {
-  return {a.add<uint16_t>(c.posinfo.size()), a.add<uint32_t>(c.p.dwell_k), a.add<uint8_t>(sizeof c.bc)};
+SimTables sim_tables(Arena& a, const SimCall& c, const SimPoolHost* pool, size_t n_reads) {
+  SimTables t{a.add<uint16_t>(c.posinfo.size()), a.add<uint32_t>(c.p.dwell_k), a.add<uint8_t>(sizeof c.bc), {}, {}, {}, {}};
+  if (pool) {
+    t.pool = a.add<uint8_t>((size_t)pool->n * c.p.msg_len);
+    if (pool->cdf) t.pool_cdf = a.add<uint32_t>((size_t)pool->n);
+    t.source = a.add<int32_t>(n_reads);
+    t.rc = a.add<uint8_t>(n_reads);
+  }
+  return t;
 }
-// c and dwell_cdf outlive the call's StreamDrain
-int upload_sim_tables(lva_decoder* d, const Arena& a, const SimTables& t, const SimCall& c, const uint32_t* dwell_cdf) {
+// c, dwell_cdf and the pool outlive the call's StreamDrain.  *dev: the pool as the kernel takes it (pool == null: untouched)
+int upload_sim_tables(lva_decoder* d, const Arena& a, const SimTables& t, const SimCall& c, const uint32_t* dwell_cdf,
+                      const SimPoolHost* pool, SimPool* dev) {
   HIP_TRY(hipMemcpyAsync(a.ptr(t.posinfo), c.posinfo.data(), 2 * c.posinfo.size(), hipMemcpyHostToDevice, d->stream));
   HIP_TRY(hipMemcpyAsync(a.ptr(t.cdf), dwell_cdf, 4 * (size_t)c.p.dwell_k, hipMemcpyHostToDevice, d->stream));
   HIP_TRY(hipMemcpyAsync(a.ptr(t.bc), c.bc, sizeof c.bc, hipMemcpyHostToDevice, d->stream));
+  if (!pool) return LVA_OK;
+  HIP_TRY(hipMemcpyAsync(a.ptr(t.pool), pool->msgs, (size_t)pool->n * c.p.msg_len, hipMemcpyHostToDevice, d->stream));
+  if (pool->cdf) HIP_TRY(hipMemcpyAsync(a.ptr(t.pool_cdf), pool->cdf, 4 * (size_t)pool->n, hipMemcpyHostToDevice, d->stream));
+  dev->msgs = a.ptr(t.pool);
+  dev->cdf = a.ptr(t.pool_cdf);
+  dev->n = (uint32_t)pool->n;
+  dev->source = a.ptr(t.source);
+  dev->rc = a.ptr(t.rc);
   return LVA_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int lva_simulate_plan(lva_decoder* d, uint64_t seed, uint32_t first_read, int32_t n_reads, uint32_t sub_thr, uint32_t del_thr,
-                      uint32_t ins_thr, const uint32_t* dwell_cdf, int32_t dwell_k, const char* start_barcode,
-                      const char* end_barcode, uint32_t flank_lo, uint32_t flank_hi, int32_t rc_mode, int64_t* row_offsets_out,
-                      int64_t* base_offsets_out) {
+// the one body of lva_simulate_plan and lva_simulate_pool_plan (pool == null: the former)
+int simulate_plan(lva_decoder* d, uint64_t seed, uint32_t first_read, int32_t n_reads, uint32_t sub_thr, uint32_t del_thr,
+                  uint32_t ins_thr, const uint32_t* dwell_cdf, int32_t dwell_k, const char* start_barcode, const char* end_barcode,
+                  uint32_t flank_lo, uint32_t flank_hi, int32_t rc_mode, const SimPoolHost* pool, int64_t* row_offsets_out,
+                  int64_t* base_offsets_out) {
   SimCall c;
-  int st = sim_args(d, seed, first_read, n_reads, sub_thr, del_thr, ins_thr, dwell_cdf, dwell_k, rc_mode, &c);
+  int st = sim_args(d, seed, first_read, n_reads, sub_thr, del_thr, ins_thr, dwell_cdf, dwell_k, rc_mode, pool, &c);
   if (st == LVA_OK && (!row_offsets_out || !base_offsets_out)) st = LVA_ERR_ARG;
   if (st != LVA_OK) return st;
   if ((st = sim_barcodes(start_barcode, end_barcode, flank_lo, flank_hi, &c)) != LVA_OK) return st;
@@ -755,13 +793,15 @@ int lva_simulate_plan(lva_decoder* d, uint64_t seed, uint32_t first_read, int32_
   const size_t n = (size_t)n_reads;
   std::vector<int32_t> lens(2 * n);
   Arena arena;
-  const SimTables tab = sim_tables(arena, c);
+  const SimTables tab = sim_tables(arena, c, pool, n);
   const auto d_lens = arena.add<int32_t>(2 * n);
   if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
   StreamDrain drain(d->stream);
-  if ((st = upload_sim_tables(d, arena, tab, c, dwell_cdf)) != LVA_OK) return st;
-  const int e = launch_sim_strand(c.p, n_reads, arena.ptr(tab.posinfo), arena.ptr(tab.cdf), arena.ptr(tab.bc), nullptr, nullptr,
-                                  arena.ptr(d_lens), nullptr, nullptr, nullptr, nullptr, d->stream);
+  SimPool dpool;
+  if ((st = upload_sim_tables(d, arena, tab, c, dwell_cdf, pool, &dpool)) != LVA_OK) return st;
+  const int e = launch_sim_strand(c.p, pool ? &dpool : nullptr, n_reads, arena.ptr(tab.posinfo), arena.ptr(tab.cdf),
+                                  arena.ptr(tab.bc), nullptr, nullptr, arena.ptr(d_lens), nullptr, nullptr, nullptr, nullptr,
+                                  d->stream);
   if (e) return launch_status(e);
   HIP_TRY(hipMemcpyAsync(lens.data(), arena.ptr(d_lens), 8 * n, hipMemcpyDeviceToHost, d->stream));
   if ((st = drain.finish()) != LVA_OK) return st;
@@ -774,14 +814,14 @@ int lva_simulate_plan(lva_decoder* d, uint64_t seed, uint32_t first_read, int32_
   return check_offsets(row_offsets_out, n_reads, &T);
 }
 
-int lva_simulate_fill_device(lva_decoder* d, uint64_t seed, uint32_t first_read, int32_t n_reads, uint32_t sub_thr,
-                             uint32_t del_thr, uint32_t ins_thr, const uint32_t* dwell_cdf, int32_t dwell_k,
-                             const char* start_barcode, const char* end_barcode, uint32_t flank_lo, uint32_t flank_hi,
-                             int32_t rc_mode, float scale, float margin, float clip, const int64_t* row_offsets,
-                             const int64_t* base_offsets, float* scores_dev, uint8_t* msgs_out, uint8_t* bases_out,
-                             uint8_t* true_idx_out) {
+// the one body of lva_simulate_fill_device and lva_simulate_pool_fill_device (pool == null: the former)
+int simulate_fill(lva_decoder* d, uint64_t seed, uint32_t first_read, int32_t n_reads, uint32_t sub_thr, uint32_t del_thr,
+                  uint32_t ins_thr, const uint32_t* dwell_cdf, int32_t dwell_k, const char* start_barcode, const char* end_barcode,
+                  uint32_t flank_lo, uint32_t flank_hi, int32_t rc_mode, const SimPoolHost* pool, float scale, float margin,
+                  float clip, const int64_t* row_offsets, const int64_t* base_offsets, float* scores_dev, uint8_t* msgs_out,
+                  uint8_t* bases_out, uint8_t* true_idx_out, int32_t* source_out, uint8_t* rc_out) {
   SimCall c;
-  int st = sim_args(d, seed, first_read, n_reads, sub_thr, del_thr, ins_thr, dwell_cdf, dwell_k, rc_mode, &c);
+  int st = sim_args(d, seed, first_read, n_reads, sub_thr, del_thr, ins_thr, dwell_cdf, dwell_k, rc_mode, pool, &c);
   if (st != LVA_OK) return st;
   if (!row_offsets || !base_offsets || !(clip > 0.0f) || scale != scale || margin != margin) return LVA_ERR_ARG;
   size_t T = 0, B = 0;
@@ -794,19 +834,20 @@ int lva_simulate_fill_device(lva_decoder* d, uint64_t seed, uint32_t first_read,
   const size_t n = (size_t)n_reads, mb = n * c.p.msg_len;
   int32_t bad = 0;
   Arena arena;
-  const SimTables tab = sim_tables(arena, c);
+  const SimTables tab = sim_tables(arena, c, pool, n);
   const auto d_row = arena.add<int64_t>(n + 1), d_base = arena.add<int64_t>(n + 1);
   const auto d_msgs = arena.add<uint8_t>(mb), d_bases = arena.add<uint8_t>(B), d_tidx = arena.add<uint8_t>(T);
   const auto d_bad = arena.add<int32_t>(1);
   if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
   StreamDrain drain(d->stream);
-  if ((st = upload_sim_tables(d, arena, tab, c, dwell_cdf)) != LVA_OK) return st;
+  SimPool dpool;
+  if ((st = upload_sim_tables(d, arena, tab, c, dwell_cdf, pool, &dpool)) != LVA_OK) return st;
   HIP_TRY(hipMemcpyAsync(arena.ptr(d_row), row_offsets, 8 * (n + 1), hipMemcpyHostToDevice, d->stream));
   HIP_TRY(hipMemcpyAsync(arena.ptr(d_base), base_offsets, 8 * (n + 1), hipMemcpyHostToDevice, d->stream));
   HIP_TRY(hipMemsetAsync(arena.ptr(d_bad), 0, sizeof(int32_t), d->stream));
-  int e = launch_sim_strand(c.p, n_reads, arena.ptr(tab.posinfo), arena.ptr(tab.cdf), arena.ptr(tab.bc), arena.ptr(d_row),
-                            arena.ptr(d_base), nullptr, arena.ptr(d_msgs), arena.ptr(d_bases), arena.ptr(d_tidx), arena.ptr(d_bad),
-                            d->stream);
+  int e = launch_sim_strand(c.p, pool ? &dpool : nullptr, n_reads, arena.ptr(tab.posinfo), arena.ptr(tab.cdf), arena.ptr(tab.bc),
+                            arena.ptr(d_row), arena.ptr(d_base), nullptr, arena.ptr(d_msgs), arena.ptr(d_bases), arena.ptr(d_tidx),
+                            arena.ptr(d_bad), d->stream);
   if (e) return launch_status(e);
   HIP_TRY(hipEventRecord(d->ev_total0, d->stream));
   e = launch_sim_scores(c.p, n_reads, arena.ptr(d_row), (uint32_t)T, arena.ptr(d_tidx), scale, margin, clip, scores_dev, d->stream);
@@ -815,10 +856,57 @@ int lva_simulate_fill_device(lva_decoder* d, uint64_t seed, uint32_t first_read,
   HIP_TRY(hipMemcpyAsync(msgs_out, arena.ptr(d_msgs), mb, hipMemcpyDeviceToHost, d->stream));
   if (bases_out && B) HIP_TRY(hipMemcpyAsync(bases_out, arena.ptr(d_bases), B, hipMemcpyDeviceToHost, d->stream));
   if (true_idx_out && T) HIP_TRY(hipMemcpyAsync(true_idx_out, arena.ptr(d_tidx), T, hipMemcpyDeviceToHost, d->stream));
+  if (pool && source_out) HIP_TRY(hipMemcpyAsync(source_out, arena.ptr(tab.source), 4 * n, hipMemcpyDeviceToHost, d->stream));
+  if (pool && rc_out) HIP_TRY(hipMemcpyAsync(rc_out, arena.ptr(tab.rc), n, hipMemcpyDeviceToHost, d->stream));
   HIP_TRY(hipMemcpyAsync(&bad, arena.ptr(d_bad), sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
   if ((st = drain.finish()) != LVA_OK) return st;
   if ((st = tp_profile(d, T, true)) != LVA_OK) return st;
   return bad ? LVA_ERR_ARG : LVA_OK;           // the offsets are not this call's plan: nothing was written outside them
+}
+
+}  // namespace
+
+extern "C" {
+
+int lva_simulate_plan(lva_decoder* d, uint64_t seed, uint32_t first_read, int32_t n_reads, uint32_t sub_thr, uint32_t del_thr,
+                      uint32_t ins_thr, const uint32_t* dwell_cdf, int32_t dwell_k, const char* start_barcode,
+                      const char* end_barcode, uint32_t flank_lo, uint32_t flank_hi, int32_t rc_mode, int64_t* row_offsets_out,
+                      int64_t* base_offsets_out) {
+  return simulate_plan(d, seed, first_read, n_reads, sub_thr, del_thr, ins_thr, dwell_cdf, dwell_k, start_barcode, end_barcode,
+                       flank_lo, flank_hi, rc_mode, nullptr, row_offsets_out, base_offsets_out);
+}
+
+int lva_simulate_fill_device(lva_decoder* d, uint64_t seed, uint32_t first_read, int32_t n_reads, uint32_t sub_thr,
+                             uint32_t del_thr, uint32_t ins_thr, const uint32_t* dwell_cdf, int32_t dwell_k,
+                             const char* start_barcode, const char* end_barcode, uint32_t flank_lo, uint32_t flank_hi,
+                             int32_t rc_mode, float scale, float margin, float clip, const int64_t* row_offsets,
+                             const int64_t* base_offsets, float* scores_dev, uint8_t* msgs_out, uint8_t* bases_out,
+                             uint8_t* true_idx_out) {
+  return simulate_fill(d, seed, first_read, n_reads, sub_thr, del_thr, ins_thr, dwell_cdf, dwell_k, start_barcode, end_barcode,
+                       flank_lo, flank_hi, rc_mode, nullptr, scale, margin, clip, row_offsets, base_offsets, scores_dev, msgs_out,
+                       bases_out, true_idx_out, nullptr, nullptr);
+}
+
+int lva_simulate_pool_plan(lva_decoder* d, uint64_t seed, uint32_t first_read, int32_t n_reads, uint32_t sub_thr, uint32_t del_thr,
+                           uint32_t ins_thr, const uint32_t* dwell_cdf, int32_t dwell_k, const char* start_barcode,
+                           const char* end_barcode, uint32_t flank_lo, uint32_t flank_hi, int32_t rc_mode, const uint8_t* pool,
+                           int32_t n_pool, const uint32_t* pool_cdf, int64_t* row_offsets_out, int64_t* base_offsets_out) {
+  const SimPoolHost ph{pool, n_pool, pool_cdf};
+  return simulate_plan(d, seed, first_read, n_reads, sub_thr, del_thr, ins_thr, dwell_cdf, dwell_k, start_barcode, end_barcode,
+                       flank_lo, flank_hi, rc_mode, &ph, row_offsets_out, base_offsets_out);
+}
+
+int lva_simulate_pool_fill_device(lva_decoder* d, uint64_t seed, uint32_t first_read, int32_t n_reads, uint32_t sub_thr,
+                                  uint32_t del_thr, uint32_t ins_thr, const uint32_t* dwell_cdf, int32_t dwell_k,
+                                  const char* start_barcode, const char* end_barcode, uint32_t flank_lo, uint32_t flank_hi,
+                                  int32_t rc_mode, const uint8_t* pool, int32_t n_pool, const uint32_t* pool_cdf, float scale,
+                                  float margin, float clip, const int64_t* row_offsets, const int64_t* base_offsets,
+                                  float* scores_dev, uint8_t* msgs_out, uint8_t* bases_out, uint8_t* true_idx_out,
+                                  int32_t* source_out, uint8_t* rc_out) {
+  const SimPoolHost ph{pool, n_pool, pool_cdf};
+  return simulate_fill(d, seed, first_read, n_reads, sub_thr, del_thr, ins_thr, dwell_cdf, dwell_k, start_barcode, end_barcode,
+                       flank_lo, flank_hi, rc_mode, &ph, scale, margin, clip, row_offsets, base_offsets, scores_dev, msgs_out,
+                       bases_out, true_idx_out, source_out, rc_out);
 }
 
 }  // extern "C"

@@ -7,8 +7,9 @@
 
 namespace lva {
 
-// the streams: 0..4 the read simulator (simulate.py), 5 the trial order (trials.py)
-constexpr uint32_t kStreamMessage = 0, kStreamChannel = 1, kStreamDwell = 2, kStreamNoise = 3, kStreamLead = 4, kStreamTrial = 5;
+// the streams: 0..4 and 6 the read simulator (simulate.py), 5 the trial order (trials.py)
+constexpr uint32_t kStreamMessage = 0, kStreamChannel = 1, kStreamDwell = 2, kStreamNoise = 3, kStreamLead = 4, kStreamTrial = 5,
+                   kStreamSource = 6;
 
 constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u, kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
 

@@ -78,6 +78,23 @@ def filter_all(a, num_oligos):
     return index, payload
 
 
+def print_curve(sizes, list_size, num_trials, trial, out):
+    """the reference's lines, once per sample size: trial(k, t) -> whether trial t of sizes[k] recovered the file, asked in
+    the order printed.  -> the successes of the last size"""
+    num_successes = 0
+    for k, num_reads_to_use in enumerate(sizes):
+        print("NUM_READS_TO_USE:", num_reads_to_use, file=out)
+        print("list size:", list_size, file=out)
+        num_successes = 0
+        for t in range(num_trials):
+            ok = trial(k, t)
+            num_successes += int(ok)
+            print("Success" if ok else "Failure", file=out)
+        print("NUM_TRIALS", num_trials, file=out)
+        print("num_successes", num_successes, file=out)
+    return num_successes
+
+
 def main(argv=None, out=sys.stdout):
     parser = build_parser()
     a = parser.parse_args(argv)
@@ -94,25 +111,17 @@ def main(argv=None, out=sys.stdout):
         index, payload = filter_all(a, num_oligos)
         stats = trials.run_trials(index, payload, original, a.bytes_per_oligo, num_oligos_RS, num_oligos, a.num_reads_to_use,
                                   a.num_trials, a.seed, device=a.device)
-    num_successes = 0
-    for k, num_reads_to_use in enumerate(a.num_reads_to_use):
-        print("NUM_READS_TO_USE:", num_reads_to_use, file=out)
-        print("list size:", a.list_size, file=out)
-        num_successes = 0
-        for t in range(a.num_trials):
-            if a.trials == "device":
-                ok = bool(stats[k, t, 3])
-            else:
-                lists = [lst for lst in (read_list(a, i) for i in rnd.sample(list(range(a.num_reads_total)), num_reads_to_use))
-                         if lst is not None]
-                data, passed = rs_code.decode_from_lists(lists, a.bytes_per_oligo, num_oligos_RS, num_oligos, pad=a.pad, device=a.device,
-                                                         list_ops=a.list_ops)
-                ok = passed > 0 and data[:data_file_size] == original     # no read passed the filter: the reference dies in MainDecoder
-            num_successes += int(ok)
-            print("Success" if ok else "Failure", file=out)
-        print("NUM_TRIALS", a.num_trials, file=out)
-        print("num_successes", num_successes, file=out)
-    return num_successes
+
+    def trial(k, t):
+        if a.trials == "device":
+            return bool(stats[k, t, 3])
+        lists = [lst for lst in (read_list(a, i) for i in rnd.sample(list(range(a.num_reads_total)), a.num_reads_to_use[k]))
+                 if lst is not None]
+        data, passed = rs_code.decode_from_lists(lists, a.bytes_per_oligo, num_oligos_RS, num_oligos, pad=a.pad, device=a.device,
+                                                 list_ops=a.list_ops)
+        return passed > 0 and data[:data_file_size] == original     # no read passed the filter: the reference dies in MainDecoder
+
+    return print_curve(a.num_reads_to_use, a.list_size, a.num_trials, trial, out)
 
 
 if __name__ == "__main__":

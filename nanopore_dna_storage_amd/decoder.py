@@ -448,40 +448,49 @@ class Decoder:
 
     # --- reads made on the device (simulate.py is the definition) ----------------
     @contextmanager
-    def simulate(self, n, seed, first_read=0, **kw):
+    def simulate(self, n, seed, first_read=0, pool=None, pool_cdf=None, **kw):
         """n simulated reads of this decoder's code, numbers first_read .. first_read + n - 1 under `seed`, as transition
         scores in HBM for the length of a `with` block -> (device pointer, row_offsets, truth); truth: dict(msgs uint8
         [n, msg_len], bases uint8, base_offsets int64 [n + 1], true_idx uint8 [blocks]).  Keywords (simulate.parameters): sub,
         dele, ins, margin, sigma, clip, dwell_cdf, start_barcode, end_barcode, flank, rc_mode.  Bit for bit what
-        simulate.reference_reads gives for the same arguments; a read depends on (seed, read number) alone."""
+        simulate.reference_reads gives for the same arguments; a read depends on (seed, read number) alone.
+        pool (uint8 [n_pool, msg_len] of 0 / 1): every read's message is a pool entry, drawn uniformly or by pool_cdf
+        (simulate.weights_to_cdf); rc_mode may then be 3, a coin per read; truth gains source int32 [n] and rc uint8 [n]."""
         from . import simulate as sim
-        q = sim.parameters(**kw)
+        q, pool, pool_cdf = sim.call_parameters(self.msg_len, pool, pool_cdf, kw)
         if n < 0 or first_read < 0 or first_read + n > 1 << 32:
             raise ValueError("read numbers are 32-bit")
         cdf = q["cdf"]
         bc = [None if b is None else b.encode() for b in (q["start_barcode"], q["end_barcode"])]
         shared = (self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_read), int(n), q["sub"], q["dele"], q["ins"], cdf.ctypes.data,
                   len(cdf), bc[0], bc[1], q["flank"][0], q["flank"][1], q["rc_mode"])
+        plan, fill, drawn, more = self._L.lva_simulate_plan, self._L.lva_simulate_fill_device, (), {}
+        if pool is not None:                      # the pool pair: the same arguments, the pool behind them, two more outputs
+            plan, fill = self._L.lva_simulate_pool_plan, self._L.lva_simulate_pool_fill_device
+            shared += (pool.ctypes.data, len(pool), None if pool_cdf is None else pool_cdf.ctypes.data)
+            more = dict(source=np.zeros(n, np.int32), rc=np.zeros(n, np.uint8))
+            drawn = (more["source"].ctypes.data, more["rc"].ctypes.data)
         row, base = np.zeros(max(n, 0) + 1, np.int64), np.zeros(max(n, 0) + 1, np.int64)
-        self._check(self._L.lva_simulate_plan(*shared, row.ctypes.data, base.ctypes.data))
+        self._check(plan(*shared, row.ctypes.data, base.ctypes.data))
         msgs = np.zeros((n, self.msg_len), np.uint8)
         bases, true_idx = np.zeros(max(int(base[-1]), 1), np.uint8), np.zeros(max(int(row[-1]), 1), np.uint8)
         with self.resident(max(int(row[-1]), 1) * 160) as (dev, _):
-            self._check(self._L.lva_simulate_fill_device(*shared, float(q["scale"]), float(q["margin"]), float(q["clip"]),
-                                                         row.ctypes.data, base.ctypes.data, dev, msgs.ctypes.data,
-                                                         bases.ctypes.data, true_idx.ctypes.data))
-            yield dev, row, dict(msgs=msgs, bases=bases[:int(base[-1])], base_offsets=base, true_idx=true_idx[:int(row[-1])])
+            self._check(fill(*shared, float(q["scale"]), float(q["margin"]), float(q["clip"]), row.ctypes.data, base.ctypes.data,
+                             dev, msgs.ctypes.data, bases.ctypes.data, true_idx.ctypes.data, *drawn))
+            yield dev, row, dict(msgs=msgs, bases=bases[:int(base[-1])], base_offsets=base, true_idx=true_idx[:int(row[-1])],
+                                 **more)
 
-    def simulate_and_decode(self, n, seed, first_read=0, **kw):
+    def simulate_and_decode(self, n, seed, first_read=0, pool=None, pool_cdf=None, **kw):
         """simulate -> posteriors in place -> decode (with both barcodes: locate_payload_resident -> decode_located) without
         the scores leaving the device -> (truth, results); results as decode() / decode_with_barcodes() give them.  Without
-        barcodes the orientation of every read is passed to the decoder as the simulator chose it (rc_mode)."""
-        with self.simulate(n, seed, first_read, **kw) as (dev, off, truth):
+        barcodes the orientation of every read is passed to the decoder as the simulator chose it (rc_mode; with a pool,
+        truth's rc, as drawn)."""
+        with self.simulate(n, seed, first_read, pool=pool, pool_cdf=pool_cdf, **kw) as (dev, off, truth):
             self.posteriors_resident(dev, off)
             if kw.get("start_barcode") is not None:
                 return truth, self._decode_chain_resident(dev, off, None, kw["start_barcode"], kw["end_barcode"])
             mode = kw.get("rc_mode", 0)
-            rc = [mode == 1 or (mode == 2 and bool((first_read + i) & 1)) for i in range(n)]
+            rc = [mode == 1 or (mode == 2 and bool((first_read + i) & 1)) for i in range(n)] if pool is None else truth["rc"]
             return truth, self.decode_resident(dev, off, rc)
 
     # --- decode stream: reads go in one at a time, results come out as they finish -------------

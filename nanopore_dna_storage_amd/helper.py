@@ -269,10 +269,17 @@ def encode(data_file, oligo_file, bytes_per_oligo, RS_redundancy, conv_m, conv_r
     return oligos
 
 
+def read_conv_input(path):
+    """the bit strings helper.encode writes beside the oligo file -> uint8 [num_oligos, msg_len] of 0 / 1"""
+    with open(path) as f:
+        rows = [ln.strip() for ln in f if ln.strip()]
+    return np.array([np.frombuffer(r.encode("ascii"), np.uint8) - 48 for r in rows], dtype=np.uint8)
+
+
 def simulate_and_decode(oligo_file, decoded_data_file, num_reads, data_file_size, bytes_per_oligo, RS_redundancy, conv_m, conv_r,
                         pad=False, syn_sub_prob=0.005, syn_del_prob=0.005, syn_ins_prob=0.0005, deepsimdwell=False, num_thr=16,
                         list_size=1, seed=None, margin=6.0, device=0, out=None, decoder=None, posterior_source="softmax",
-                        list_ops="host"):
+                        list_ops="host", chunk=4096):
     """helper.py:275-350, same arguments: num_reads times pick a random oligo and orientation, pass it through the
     substitution / deletion / insertion channel, turn it into a posterior matrix, decode a list of list_size candidates,
     take the first candidate whose CRC-8 checks and whose index is in range (the first payload seen for an index stands,
@@ -282,7 +289,10 @@ def simulate_and_decode(oligo_file, decoded_data_file, num_reads, data_file_size
     on the GPU instead of one decoder process per read.  seed: numpy seed (the reference draws from the global state).
     posterior_source: "softmax" -- every block's posteriors are the log-softmax of independent logits; "crf" -- what a
     flip-flop CRF network gives: transition scores (synth.scores_from_bases) that go through Decoder.decode_from_scores,
-    forward-backward posteriors and decode without leaving the device.
+    forward-backward posteriors and decode without leaving the device; "device" -- the reads themselves are made on the
+    device (Decoder.simulate_and_decode with a pool: simulate.py's stream 6 picks the oligo and the orientation of read number
+    k from the bit strings of oligo_file + ".conv_input", the syn_*_prob arguments are the channel, `seed` is the Philox seed
+    and must be given), `chunk` reads at a time, so that the scores in HBM stay bounded; no loop over reads on the host.
     list_ops: "host" -- the filter and the first-seen rule as the Python loops below; "device" -- the same on the GPU
     (list_ops.filter_lists, list_ops.consensus with first_only), same counts and bytes.
     -> dict(num_attempted, num_success, num_unique, decoded bytes)."""
@@ -295,12 +305,14 @@ def simulate_and_decode(oligo_file, decoded_data_file, num_reads, data_file_size
     with open(oligo_file) as f:
         oligo_list = [ln.rstrip("\n") for ln in f.readlines()]
     print("oligo_len", len(oligo_list[0]), file=out)
-    if posterior_source not in ("softmax", "crf"):
-        raise ValueError("posterior_source: 'softmax' or 'crf'")
-    crf = posterior_source == "crf"
+    if posterior_source not in ("softmax", "crf", "device"):
+        raise ValueError("posterior_source: 'softmax', 'crf' or 'device'")
+    crf, made_here = posterior_source == "crf", posterior_source != "device"
+    if not made_here and (seed is None or chunk < 1):
+        raise ValueError("posterior_source 'device': a read is a function of (seed, read number), give a seed; chunk >= 1")
     rng = np.random.default_rng(seed)
     posts, rcs = [], []
-    for _ in range(num_reads):
+    for _ in range(num_reads if made_here else 0):
         oligo = oligo_list[int(rng.integers(len(oligo_list)))]
         rc = bool(rng.integers(2))
         if rc:
@@ -311,7 +323,14 @@ def simulate_and_decode(oligo_file, decoded_data_file, num_reads, data_file_size
     own = decoder is None
     dec = Decoder(conv_m, conv_r, msg_len, list_size=list_size, max_deviation=20, device=device) if own else decoder
     try:
-        results = dec.decode_from_scores(posts, rc=rcs) if crf else dec.decode(posts, rc=rcs)
+        if made_here:
+            results = dec.decode_from_scores(posts, rc=rcs) if crf else dec.decode(posts, rc=rcs)
+        else:
+            pool = read_conv_input(oligo_file + ".conv_input")
+            results = []
+            for first in range(0, num_reads, chunk):
+                results += dec.simulate_and_decode(min(chunk, num_reads - first), seed, first_read=first, pool=pool, rc_mode=3,
+                                                   sub=syn_sub_prob, dele=syn_del_prob, ins=syn_ins_prob, margin=margin)[1]
     finally:
         if own:
             dec.close()

@@ -5,7 +5,7 @@ import numpy as np
 
 M0, M1 = 0xD2511F53, 0xCD9E8D57
 W0, W1 = 0x9E3779B9, 0xBB67AE85
-STREAM_MESSAGE, STREAM_CHANNEL, STREAM_DWELL, STREAM_NOISE, STREAM_LEAD, STREAM_TRIAL = range(6)
+STREAM_MESSAGE, STREAM_CHANNEL, STREAM_DWELL, STREAM_NOISE, STREAM_LEAD, STREAM_TRIAL, STREAM_SOURCE = range(7)
 _U32 = 0xFFFFFFFF
 
 
