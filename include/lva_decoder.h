@@ -128,6 +128,15 @@ int lva_code_tables(int32_t mem_conv, int32_t rate, uint32_t msg_len, int32_t rc
                     const char *sync_marker, uint32_t sync_period, uint32_t *pos2msg, uint8_t *ptype,
                     uint32_t *vmask, uint32_t *vval, uint16_t *predtab);
 
+/* The 32-bit message fingerprint the step kernels hold for a path that has consumed n_bits <= msg_len message bits (the
+ * de-duplication key of the fast kernels), for inspection/tests: the kernels' per-position
+ * deltas folded from the empty message.  msg_bits: msg_len bytes of 0/1 in lva_encode's order; the forward orientation
+ * consumes msg_bits[0 .. n_bits), a reverse complement (rc != 0) msg_bits[msg_len - 1] down to msg_bits[msg_len - n_bits].
+ * n_bits = msg_len goes on through the terminating bits: the fingerprint at the final position.  LVA_ERR_ARG when
+ * n_bits > msg_len or when no trellis position has consumed exactly n_bits bits (inside a two-bit position). */
+int lva_code_fingerprint(int32_t mem_conv, int32_t rate, uint32_t msg_len, int32_t rc, const char *sync_marker,
+                         uint32_t sync_period, const uint8_t *msg_bits, uint32_t n_bits, uint32_t *out);
+
 /* The band [lo, hi) of every time step of a read of nblk blocks, for inspection/tests (each output may be NULL, 2*nblk words):
  *   reference_lo_hi  as the reference computes it (:677-679, with the fused multiply-subtract of its build);
  *   working_lo_hi    what the kernels work on: the same without positions a path cannot have reached yet (> t + 1) and

@@ -101,6 +101,7 @@ ABI = {
     "lva_last_hip_error": (_cp, []),
     "lva_code_describe": (_int, _code + [ctypes.POINTER(CodeInfoStruct)]),
     "lva_code_tables": (_int, _code + [_vp, _vp, _vp, _vp, _vp]),
+    "lva_code_fingerprint": (_int, _code + [_vp, _u32, _vp]),
     "lva_band_table": (_int, _code + [_u32, _u32, _vp, _vp]),
     "lva_encode": (_int, [_i32, _i32, _u32, _vp, _i32, _vp]),
     "lva_algorithmic_bytes": (_int, _code + [_u32, _u32, _u32, ctypes.POINTER(ctypes.c_double)]),

@@ -90,6 +90,14 @@ int lva_code_tables(int32_t mem_conv, int32_t rate, uint32_t msg_len, int32_t rc
   return LVA_OK;
 }
 
+int lva_code_fingerprint(int32_t mem_conv, int32_t rate, uint32_t msg_len, int32_t rc, const char* sync_marker,
+                         uint32_t sync_period, const uint8_t* msg_bits, uint32_t n_bits, uint32_t* out) {
+  Code c;
+  const int st = build_code(&c, mem_conv, rate, msg_len, rc, sync_marker, sync_period);
+  if (st != LVA_OK) return st;
+  return c.fingerprint(msg_bits, n_bits, out);
+}
+
 int lva_encode(int32_t mem_conv, int32_t rate, uint32_t msg_len, const uint8_t* msgs, int32_t n_msgs,
                uint8_t* out_bases) {
   if (n_msgs < 0 || (n_msgs > 0 && (!msgs || !out_bases))) return LVA_ERR_ARG;

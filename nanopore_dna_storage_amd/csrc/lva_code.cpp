@@ -209,6 +209,26 @@ int Code::encode(const uint8_t* msg, uint8_t* bases_out) const {
   return k == 2 * total ? LVA_OK : LVA_ERR_MSG_LEN;                                             // :496-497
 }
 
+int Code::fingerprint(const uint8_t* msg, uint32_t n_bits, uint32_t* out) const {
+  if (n_bits > msg_len || (n_bits > 0 && !msg)) return LVA_ERR_ARG;
+  const uint32_t upto = n_bits == msg_len ? msg_bits() : n_bits;   // a whole message: on through the terminating bits
+  // bit i in order of consumption: the message forwards, or backwards for a reverse complement, then the terminating bits
+  auto bit = [&](uint32_t i) -> uint32_t {
+    if (i >= msg_len) return (fin >> (i - msg_len)) & 1u;
+    return (uint32_t)(msg[rc ? msg_len - 1 - i : i] & 1);
+  };
+  uint32_t fp = 0, pos = 0;                                        // lva_init_slot: the empty message has fingerprint 0
+  while (nbits[pos] < upto) {
+    ++pos;                                                         // (nbits[npos - 1] = msg_bits(): pos stays below npos)
+    const uint32_t n0 = nbits[pos - 1];
+    if (nbits[pos] > upto) return LVA_ERR_ARG;                     // n_bits ends inside a two-bit position: no path holds that
+    const uint32_t nb = shift_of(ptype[pos]) == 1 ? bit(n0) : 2 * bit(n0) + bit(n0 + 1);   // resolve_target's newbits
+    fp ^= fpc[pos][nb];
+  }
+  if (out) *out = fp;
+  return LVA_OK;
+}
+
 void Code::band(uint32_t t, uint32_t nblk, uint32_t max_dev, uint32_t* lo, uint32_t* hi) const {
   // :677-679.  `(double)t / nblk * nstate_pos - max_deviation` is contracted to one fused
   // multiply-subtract by g++ -O3 -march=native (install.sh:9) on FMA hosts, and the reference

@@ -53,6 +53,11 @@ struct Code {
   uint32_t out_bit(int k, uint32_t st, uint32_t bit) const;
   // conv_encode (:450-499); msg: msg_len values 0/1; bases_out: oligo_len() values 0..3
   int encode(const uint8_t* msg, uint8_t* bases_out) const;
+  // the fingerprint (lva_device.h) the step kernels hold for a path that has consumed n_bits <= msg_len message bits: fpc folded
+  // along the positions from the empty message.  msg: the message in encode()'s order; the forward orientation consumes
+  // msg[0 .. n_bits), a reverse complement msg[msg_len - 1] down to msg[msg_len - n_bits].  n_bits = msg_len goes on through the
+  // terminating bits to the final position.  LVA_ERR_ARG when no position has consumed exactly n_bits bits.
+  int fingerprint(const uint8_t* msg, uint32_t n_bits, uint32_t* out) const;
   // band of time step t (:677-679) as the reference binary evaluates it (fused multiply-subtract)
   void band(uint32_t t, uint32_t nblk, uint32_t max_dev, uint32_t* lo, uint32_t* hi) const;
   // algorithmic bytes of one read: sum_t [2*R(t)*L*(4+4W) + 160]

@@ -64,6 +64,20 @@ def code_tables(mem_conv, rate, msg_len, rc=False, sync_marker="", sync_period=0
     return dict(pos2msg=pos2msg, ptype=ptype, vmask=vmask, vval=vval, predtab=predtab)
 
 
+def code_fingerprint(mem_conv, rate, msg_len, msg_bits, n_bits=None, rc=False, sync_marker="", sync_period=0):
+    """The 32-bit fingerprint the step kernels hold for a path that has consumed the first n_bits (default: all, and then the
+    terminating bits too) of the message `msg_bits` (msg_len values 0/1 in encode()'s order; a reverse complement consumes
+    them from the far end): lva_code_fingerprint, for inspection and tests."""
+    msg = np.ascontiguousarray(msg_bits, dtype=np.uint8)
+    if msg.shape != (msg_len,):
+        raise LvaError(-10, "Message length does not match msg_len parameter.")
+    out = ctypes.c_uint32(0)
+    check(load_library().lva_code_fingerprint(mem_conv, rate, msg_len, int(bool(rc)), _sm(sync_marker), sync_period,
+                                              msg.ctypes.data, msg_len if n_bits is None else int(n_bits), ctypes.byref(out)),
+          detail=None)
+    return out.value
+
+
 STEP_KERNELS = ("exact", "wave", "wave_wide", "acs", "fast", "lazy", "big", "big_rec")     # LVA_STEP_* of include/lva_decoder.h
 FIXUP_KERNELS = ("none", "wave", "lazy")                                                    # LVA_FIXUP_*
 
