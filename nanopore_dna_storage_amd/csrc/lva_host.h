@@ -70,6 +70,9 @@ struct lva_decoder {
 };
 
 namespace lva {
+// The two below serve lva_api.cpp's decode path alone; a side stage owns its stream, allocation and drain through one
+// Frame (lva_stages.cpp), whose destructor keeps the order that these two leave to their caller.
+//
 // From its construction on, every exit of a call leaves with the stream drained: pending copies read and write host buffers
 // and device blocks that die with the call's frame.  Construct it before the first asynchronous call and AFTER every such
 // buffer and block (locals are destroyed in reverse order).
@@ -85,7 +88,7 @@ struct StreamDrain {
   }
 };
 
-// a device copy of the caller's host posteriors (or scores) for the length of a call
+// a device copy of the caller's host posteriors for the length of lva_decode_batch
 struct HostPost {
   float* dev = nullptr;
   ~HostPost() { if (dev) (void)hipFree(dev); }

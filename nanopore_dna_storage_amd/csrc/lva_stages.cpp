@@ -1,6 +1,8 @@
 // lva_stages.cpp -- C ABI (include/lva_decoder.h) of the stages beside the list decoder: transition posteriors (N0), basecall
-// and barcode localisation (N3), demultiplexing (N3'), the consumers of a decoded list (N2), reading-cost trials (N4'), the read simulator (S).  No algorithm lives here: an entry
-// point checks its arguments, declares its device pieces, uploads, launches, copies back and waits, all through the functions below.
+// and barcode localisation (N3), demultiplexing (N3'), the consumers of a decoded list (N2), the Reed-Solomon outer code (N4),
+// reading-cost trials (N4'), the read simulator (S).  No algorithm lives here: an entry point checks its arguments, then works
+// through one Frame (below): it declares its device pieces together with their host side, begins (allocate, upload),
+// launches, finishes (copy back, wait).
 #include <algorithm>
 #include <cstring>
 
@@ -8,6 +10,7 @@
 #include "bc_kernels.h"
 #include "tp_kernels.h"
 #include "ls_kernels.h"
+#include "rs_kernels.h"
 #include "sim_kernels.h"
 #include "tr_kernels.h"
 
@@ -53,37 +56,85 @@ int stage_enter(lva_decoder* d, const int64_t* offsets, int32_t n, size_t* total
   return check_offsets(offsets, n, total) != LVA_OK ? LVA_ERR_ARG : stage_enter(d, n == 0);
 }
 
-// One device allocation for the length of a call, carved into 256-byte aligned and padded pieces.  The pieces are
-// declared first (add), alloc() sizes the block from what was declared, ptr() hands them out: the capacity cannot
-// disagree with the pieces.  Declare it before the call's StreamDrain, so that it is freed behind the drain.
-class Arena {
-  static constexpr size_t kAbsent = ~(size_t)0;
+// What one side-stage call owns on the device: the stream it works on, ONE allocation carved into 256-byte aligned and
+// padded pieces, and the drain.  A piece is declared once, with its host side: in (uploaded by begin), out (copied back by
+// finish; a null host pointer: no copy), inout (both, two host addresses), scratch (neither).  begin() sizes the block from
+// what was declared and every whole-piece copy takes its bytes from the declaration: neither can disagree with a piece.
+// The destructor drains, then frees, then destroys an owned stream, on every exit.  Host buffers that the copies read or
+// write are declared before the frame, so that they die after it.
+class Frame {
+  struct Side { size_t at, bytes; const void* src; void* dst; };
 
  public:
-  template <typename T> struct Piece { size_t at = kAbsent; };   // default: a piece that was not asked for, ptr() = null
-  Arena() = default;
-  Arena(const Arena&) = delete;
-  ~Arena() { if (base_) (void)hipFree(base_); }
+  // Converts to its typed device pointer, valid from begin() on.  Default: a piece that was not asked for, a null pointer.
+  template <typename T> struct Piece {
+    const Frame* f = nullptr;
+    size_t at = 0, count = 0;
+    T* ptr() const { return f ? reinterpret_cast<T*>(f->base_ + at) : nullptr; }
+    operator T*() const { return ptr(); }
+  };
+  Frame() = default;                                   // a device-ordinal call: open() makes the stream
+  explicit Frame(hipStream_t decoder_stream) : s_(decoder_stream) {}
+  Frame(const Frame&) = delete;
+  ~Frame() {
+    if (!done_ && s_) (void)hipStreamSynchronize(s_);
+    if (base_) (void)hipFree(base_);
+    if (own_) (void)hipStreamDestroy(s_);
+  }
+  // the device by its ordinal, and a non-blocking stream of the call's own: no decoder's stream or profile is touched
+  int open(int32_t device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return LVA_ERR_NO_DEVICE;
+    if (hipSetDevice(device) != hipSuccess) return LVA_ERR_NO_DEVICE;
+    HIP_TRY(hipStreamCreateWithFlags(&s_, hipStreamNonBlocking));
+    own_ = true;
+    return LVA_OK;
+  }
+  hipStream_t stream() const { return s_; }
   // a piece of count 0 still occupies one padded unit; ls_filter reads whole dwords up to the padded end of its messages
-  template <typename T> Piece<T> add(size_t count) {
-    Piece<T> p;
-    p.at = size_;
+  template <typename T> Piece<T> inout(const T* src, T* dst, size_t count) {
+    const Piece<T> p{this, size_, count};
+    sides_.push_back({size_, count * sizeof(T), src, dst});
     size_ += (std::max<size_t>(count, 1) * sizeof(T) + 255) & ~(size_t)255;
     return p;
   }
-  int alloc() { return hipMalloc(reinterpret_cast<void**>(&base_), size_) == hipSuccess ? LVA_OK : LVA_ERR_NOMEM; }
-  template <typename T> T* ptr(Piece<T> p) const { return p.at == kAbsent ? nullptr : reinterpret_cast<T*>(base_ + p.at); }
+  template <typename T> Piece<T> in(const T* src, size_t count) { return inout<T>(src, nullptr, count); }
+  template <typename T> Piece<T> out(T* dst, size_t count) { return inout<T>(nullptr, dst, count); }
+  template <typename T> Piece<T> scratch(size_t count) { return inout<T>(nullptr, nullptr, count); }
+  int begin() {                                        // allocate, enqueue the uploads
+    if (size_ && hipMalloc(reinterpret_cast<void**>(&base_), size_) != hipSuccess) return LVA_ERR_NOMEM;
+    for (const Side& x : sides_)
+      if (x.src && x.bytes) HIP_TRY(hipMemcpyAsync(base_ + x.at, x.src, x.bytes, hipMemcpyHostToDevice, s_));
+    return LVA_OK;
+  }
+  int finish() {                                       // the success exit: enqueue the downloads, wait, report what the wait reports
+    for (const Side& x : sides_)
+      if (x.dst && x.bytes) HIP_TRY(hipMemcpyAsync(x.dst, base_ + x.at, x.bytes, hipMemcpyDeviceToHost, s_));
+    done_ = true;
+    HIP_TRY(hipStreamSynchronize(s_));
+    return LVA_OK;
+  }
+  // The escape hatch for what is not a whole piece: bytes to or from a host address on the frame's stream ...
+  int copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, kind, s_));
+    return LVA_OK;
+  }
+  // ... and `count` elements of a piece from element `first` on, to the host
+  template <typename T> int download(T* host, Piece<T> p, size_t first, size_t count) {
+    if (first + count > p.count) { set_hip_error("Frame::download: outside the piece"); return LVA_ERR_HIP; }
+    return copy(host, p.ptr() + first, count * sizeof(T), hipMemcpyDeviceToHost);
+  }
 
  private:
+  hipStream_t s_ = nullptr;
+  bool own_ = false, done_ = false;
   char* base_ = nullptr;
   size_t size_ = 0;
+  std::vector<Side> sides_;
 };
+template <typename T> using Piece = Frame::Piece<T>;
 
-int upload_post(lva_decoder* d, const float* post, size_t blocks, HostPost* hp) {     // blocks: check_offsets' total
-  if (hipMalloc(reinterpret_cast<void**>(&hp->dev), std::max<size_t>(blocks, 1) * 160) != hipSuccess) return LVA_ERR_NOMEM;
-  if (blocks > 0) HIP_TRY(hipMemcpyAsync(hp->dev, post, blocks * 160, hipMemcpyHostToDevice, d->stream));
-  return LVA_OK;
-}
+constexpr size_t kPostRow = 40;      // floats per block of a posterior or score matrix
 
 // ---------------------------------------------------------------------------------------------
 // basecall of the posterior matrix and barcode localisation.
@@ -121,54 +172,40 @@ int make_patterns(const char* start_bc, const char* end_bc, int n_orient, BcPatt
 }
 
 // Basecalls of n reads (T blocks or bases in all) on the device, as the searches read them: made there by bc_basecall
-// (basecall_set: its working set) or the caller's own, uploaded (given_set).  Declaration order = order in the block.
+// (basecall_set: its working set, what the caller wants of it copied back) or the caller's own, uploaded (given_set; nb:
+// read_lengths).  Declaration order = order in the block.
 struct Calls {
-  Arena::Piece<int64_t> off;
-  Arena::Piece<uint32_t> tb;     // 8 back-pointer bytes per block
-  Arena::Piece<uint8_t> path;
-  Arena::Piece<char> bases;
-  Arena::Piece<uint32_t> trans;
-  Arena::Piece<int32_t> nb;
+  Piece<int64_t> off;
+  Piece<uint32_t> tb;     // 8 back-pointer bytes per block
+  Piece<uint8_t> path;
+  Piece<char> bases;
+  Piece<uint32_t> trans;
+  Piece<int32_t> nb;
 };
-Calls basecall_set(Arena& a, size_t n, size_t T) {
-  return {a.add<int64_t>(n + 1), a.add<uint32_t>(2 * T), a.add<uint8_t>(T + n), a.add<char>(T), a.add<uint32_t>(T), a.add<int32_t>(n)};
+Calls basecall_set(Frame& f, const int64_t* row_offsets, size_t n, size_t T, char* bases_out, uint32_t* trans_out, int32_t* nb_out) {
+  return {f.in(row_offsets, n + 1), f.scratch<uint32_t>(2 * T), f.scratch<uint8_t>(T + n), f.out(bases_out, T), f.out(trans_out, T),
+          f.out(nb_out, n)};
+}
+Calls given_set(Frame& f, const char* bases, const uint32_t* trans, const int64_t* base_offsets, const std::vector<int32_t>& nb, size_t T) {
+  return {f.in(base_offsets, nb.size() + 1), {}, {}, f.in(bases, T), f.in(trans, T), f.in(nb.data(), nb.size())};
 }
 
-Calls given_set(Arena& a, size_t n, size_t T) {
-  return {a.add<int64_t>(n + 1), {}, {}, a.add<char>(T), a.add<uint32_t>(T), a.add<int32_t>(n)};
+// bc_basecall over posteriors that are on the device
+int enqueue_basecall(const Frame& f, const Calls& c, const float* post_dev, int32_t n) {
+  return launch_status(launch_bc_basecall(post_dev, c.off, n, c.tb, c.path, c.bases, c.trans, c.nb, f.stream()));
 }
 
-// offsets up, bc_basecall over posteriors that are on the device
-int enqueue_basecall(lva_decoder* d, const Arena& a, const Calls& c, const float* post_dev, const int64_t* row_offsets, int32_t n) {
-  HIP_TRY(hipMemcpyAsync(a.ptr(c.off), row_offsets, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, d->stream));
-  return launch_status(launch_bc_basecall(post_dev, a.ptr(c.off), n, a.ptr(c.tb), a.ptr(c.path), a.ptr(c.bases), a.ptr(c.trans),
-                                          a.ptr(c.nb), d->stream));
-}
-
-// the caller's basecalls up; nb (read_lengths) outlives the call's StreamDrain
-int enqueue_given(lva_decoder* d, const Arena& a, const Calls& c, const char* bases, const uint32_t* trans,
-                  const int64_t* base_offsets, const std::vector<int32_t>& nb, size_t T) {
-  const size_t n = nb.size();
-  HIP_TRY(hipMemcpyAsync(a.ptr(c.off), base_offsets, 8 * (n + 1), hipMemcpyHostToDevice, d->stream));
-  if (T) HIP_TRY(hipMemcpyAsync(a.ptr(c.bases), bases, T, hipMemcpyHostToDevice, d->stream));
-  if (T) HIP_TRY(hipMemcpyAsync(a.ptr(c.trans), trans, 4 * T, hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(hipMemcpyAsync(a.ptr(c.nb), nb.data(), 4 * n, hipMemcpyHostToDevice, d->stream));
-  return LVA_OK;
-}
-
-struct LocateSet { Arena::Piece<uint32_t> best; Arena::Piece<BcResult> res; };
-LocateSet locate_set(Arena& a, size_t n) { return {a.add<uint32_t>(4 * n), a.add<BcResult>(n)}; }
-
-// bc_search + bc_finalize over basecalls that are on the device, and the copy of the windows to the caller
-int enqueue_locate(lva_decoder* d, const Arena& a, const Calls& c, const LocateSet& s, int32_t n, const BcPatterns& pat,
-                   int n_orient, uint32_t min_len, lva_payload_pos* out) {
+struct LocateSet { Piece<uint32_t> best; Piece<BcResult> res; };
+LocateSet locate_set(Frame& f, size_t n, lva_payload_pos* out) {       // out: the windows, to the caller
   static_assert(sizeof(lva_payload_pos) == sizeof(BcResult), "lva_payload_pos layout");
-  int e = launch_bc_search(a.ptr(c.bases), a.ptr(c.off), a.ptr(c.nb), n, pat, n_orient, a.ptr(s.best), d->stream);
-  if (!e) e = launch_bc_finalize(a.ptr(c.trans), a.ptr(c.off), a.ptr(c.nb), n, pat, n_orient, min_len, a.ptr(s.best), a.ptr(s.res),
-                                 d->stream);
-  if (e) return launch_status(e);
-  HIP_TRY(hipMemcpyAsync(out, a.ptr(s.res), sizeof(BcResult) * (size_t)n, hipMemcpyDeviceToHost, d->stream));
-  return LVA_OK;
+  return {f.scratch<uint32_t>(4 * n), f.out(reinterpret_cast<BcResult*>(out), n)};
+}
+
+// bc_search + bc_finalize over basecalls that are on the device
+int enqueue_locate(const Frame& f, const Calls& c, const LocateSet& s, int32_t n, const BcPatterns& pat, int n_orient, uint32_t min_len) {
+  int e = launch_bc_search(c.bases, c.off, c.nb, n, pat, n_orient, s.best, f.stream());
+  if (!e) e = launch_bc_finalize(c.trans, c.off, c.nb, n, pat, n_orient, min_len, s.best, s.res, f.stream());
+  return launch_status(e);
 }
 
 // lva_basecall_batch[_device] (n_orient = 0: no barcodes, pos_out null) and lva_locate_payload_batch[_device]
@@ -182,19 +219,14 @@ int basecall_stage(lva_decoder* d, const float* post, bool post_on_host, const i
   size_t T = 0;
   int st = stage_enter(d, row_offsets, n, &T);
   if (st != kRun) return st;
-  Arena arena;
-  HostPost hp;
-  const Calls bc = basecall_set(arena, (size_t)n, T);
-  const LocateSet loc = locate_set(arena, (size_t)n);
-  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
-  StreamDrain drain(d->stream);
-  if (post_on_host && (st = upload_post(d, post, T, &hp)) != LVA_OK) return st;
-  if ((st = enqueue_basecall(d, arena, bc, post_on_host ? hp.dev : post, row_offsets, n)) != LVA_OK) return st;
-  if (n_orient && (st = enqueue_locate(d, arena, bc, loc, n, pat, n_orient, min_len, pos_out)) != LVA_OK) return st;
-  if (bases_out && T) HIP_TRY(hipMemcpyAsync(bases_out, arena.ptr(bc.bases), T, hipMemcpyDeviceToHost, d->stream));
-  if (trans_out && T) HIP_TRY(hipMemcpyAsync(trans_out, arena.ptr(bc.trans), 4 * T, hipMemcpyDeviceToHost, d->stream));
-  if (nbases_out) HIP_TRY(hipMemcpyAsync(nbases_out, arena.ptr(bc.nb), 4 * (size_t)n, hipMemcpyDeviceToHost, d->stream));
-  return drain.finish();
+  Frame f(d->stream);
+  const Piece<float> up = post_on_host ? f.in(post, kPostRow * T) : Piece<float>{};
+  const Calls bc = basecall_set(f, row_offsets, (size_t)n, T, bases_out, trans_out, nbases_out);
+  const LocateSet loc = locate_set(f, (size_t)n, pos_out);
+  if ((st = f.begin()) != LVA_OK) return st;
+  if ((st = enqueue_basecall(f, bc, post_on_host ? up.ptr() : post, n)) != LVA_OK) return st;
+  if (n_orient && (st = enqueue_locate(f, bc, loc, n, pat, n_orient, min_len)) != LVA_OK) return st;
+  return f.finish();
 }
 
 }  // namespace
@@ -230,14 +262,12 @@ int lva_find_barcode_batch(lva_decoder* d, const char* bases, const uint32_t* tr
   int st = stage_enter(d, base_offsets, n_reads, &T);
   if (st != kRun) return st;
   const std::vector<int32_t> nb = read_lengths(base_offsets, n_reads);
-  Arena arena;
-  const Calls calls = given_set(arena, nb.size(), T);
-  const LocateSet loc = locate_set(arena, nb.size());
-  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
-  StreamDrain drain(d->stream);
-  if ((st = enqueue_given(d, arena, calls, bases, trans, base_offsets, nb, T)) != LVA_OK) return st;
-  if ((st = enqueue_locate(d, arena, calls, loc, n_reads, pat, 1, 0, out)) != LVA_OK) return st;
-  return drain.finish();
+  Frame f(d->stream);
+  const Calls calls = given_set(f, bases, trans, base_offsets, nb, T);
+  const LocateSet loc = locate_set(f, nb.size(), out);
+  if ((st = f.begin()) != LVA_OK) return st;
+  if ((st = enqueue_locate(f, calls, loc, n_reads, pat, 1, 0)) != LVA_OK) return st;
+  return f.finish();
 }
 
 }  // extern "C"
@@ -247,24 +277,23 @@ int lva_find_barcode_batch(lva_decoder* d, const char* bases, const uint32_t* tr
 // ---------------------------------------------------------------------------------------------
 namespace {
 
+// A decoder-owned block that outlives the call by design: it grows to `want` units of `unit` bytes and never shrinks.
+template <typename T> int tp_grow(lva_decoder* d, T** buf, size_t* cap, size_t want, size_t unit) {
+  if (want <= *cap) return LVA_OK;
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  if (*buf) (void)hipFree(*buf);
+  *buf = nullptr; *cap = 0;
+  if (hipMalloc(reinterpret_cast<void**>(buf), want * unit) != hipSuccess) return LVA_ERR_NOMEM;
+  *cap = want;
+  return LVA_OK;
+}
+
 // forward and backward kernel over n reads resident on the device; post_dev may be scores_dev.  Enqueues only.
-int tp_run(lva_decoder* d, const float* scores_dev, const int64_t* row_offsets, int32_t n, size_t T, float* post_dev) {
-  if (T > d->tp_fwd_cap) {
-    HIP_TRY(hipStreamSynchronize(d->stream));
-    if (d->d_tp_fwd) (void)hipFree(d->d_tp_fwd);
-    d->d_tp_fwd = nullptr; d->tp_fwd_cap = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&d->d_tp_fwd), T * 8 * sizeof(float)) != hipSuccess) return LVA_ERR_NOMEM;
-    d->tp_fwd_cap = T;
-  }
-  if ((size_t)n + 1 > d->tp_off_cap) {
-    HIP_TRY(hipStreamSynchronize(d->stream));
-    if (d->d_tp_off) (void)hipFree(d->d_tp_off);
-    d->d_tp_off = nullptr; d->tp_off_cap = 0;
-    const size_t cap = std::max<size_t>((size_t)n + 1, 1024);
-    if (hipMalloc(reinterpret_cast<void**>(&d->d_tp_off), cap * sizeof(int64_t)) != hipSuccess) return LVA_ERR_NOMEM;
-    d->tp_off_cap = cap;
-  }
-  HIP_TRY(hipMemcpyAsync(d->d_tp_off, row_offsets, 8 * ((size_t)n + 1), hipMemcpyHostToDevice, d->stream));
+int tp_run(lva_decoder* d, Frame& f, const float* scores_dev, const int64_t* row_offsets, int32_t n, size_t T, float* post_dev) {
+  int st = tp_grow(d, &d->d_tp_fwd, &d->tp_fwd_cap, T, 8 * sizeof(float));
+  if (st == LVA_OK) st = tp_grow(d, &d->d_tp_off, &d->tp_off_cap, std::max<size_t>((size_t)n + 1, 1024), sizeof(int64_t));
+  if (st == LVA_OK) st = f.copy(d->d_tp_off, row_offsets, sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice);
+  if (st != LVA_OK) return st;
   HIP_TRY(hipEventRecord(d->ev_total0, d->stream));
   int e = launch_tp_forward(scores_dev, d->d_tp_off, n, d->d_tp_fwd, d->stream);
   if (!e) e = launch_tp_backward(scores_dev, d->d_tp_off, n, d->d_tp_fwd, post_dev, d->stream);
@@ -296,13 +325,11 @@ int transpost_stage(lva_decoder* d, const float* scores, bool on_host, const int
   int st = stage_enter(d, T == 0);
   if (st == LVA_OK) return tp_profile(d, 0, false);
   if (st != kRun) return st;
-  HostPost hp;
-  StreamDrain drain(d->stream);              // the offsets are copied from the caller's memory
-  if (on_host && (st = upload_post(d, scores, T, &hp)) != LVA_OK) return st;
-  st = on_host ? tp_run(d, hp.dev, row_offsets, n, T, hp.dev) : tp_run(d, scores, row_offsets, n, T, post);
-  if (st != LVA_OK) return st;
-  if (on_host) HIP_TRY(hipMemcpyAsync(post, hp.dev, T * 160, hipMemcpyDeviceToHost, d->stream));
-  if ((st = drain.finish()) != LVA_OK) return st;
+  Frame f(d->stream);                        // (the device variant has no piece, but the offsets are copied from the caller's memory)
+  const Piece<float> io = on_host ? f.inout(scores, post, kPostRow * T) : Piece<float>{};     // up from scores, in place, down to post
+  if ((st = f.begin()) != LVA_OK) return st;
+  if ((st = tp_run(d, f, on_host ? io.ptr() : scores, row_offsets, n, T, on_host ? io.ptr() : post)) != LVA_OK) return st;
+  if ((st = f.finish()) != LVA_OK) return st;
   return tp_profile(d, T, true);
 }
 
@@ -347,32 +374,27 @@ int demux_args(const lva_experiment_barcodes* exps, int32_t n_exps, int32_t max_
 }
 
 struct DemuxSet {
-  Arena::Piece<BcPatterns> pats;
-  Arena::Piece<uint32_t> min_len;
-  Arena::Piece<uint32_t> best;
-  Arena::Piece<BcDemuxResult> res;
-  Arena::Piece<BcResult> all;    // only when the caller asks for every experiment's candidate
+  Piece<BcPatterns> pats;
+  Piece<uint32_t> min_len;
+  Piece<uint32_t> best;
+  Piece<BcDemuxResult> res;
+  Piece<BcResult> all;    // only when the caller asks for every experiment's candidate
 };
-DemuxSet demux_set(Arena& a, size_t n, size_t k, bool all) {
-  return {a.add<BcPatterns>(k), a.add<uint32_t>(k), a.add<uint32_t>(4 * n * k), a.add<BcDemuxResult>(n),
-          all ? a.add<BcResult>(n * k) : Arena::Piece<BcResult>{}};
+// x (demux_args) is declared before the frame; out, all_out: the results, to the caller
+DemuxSet demux_set(Frame& f, size_t n, const DemuxArgs& x, lva_demux_pos* out, lva_payload_pos* all_out) {
+  static_assert(sizeof(lva_demux_pos) == sizeof(BcDemuxResult), "lva_demux_pos layout");
+  const size_t k = x.pats.size();
+  return {f.in(x.pats.data(), k), f.in(x.min_len.data(), k), f.scratch<uint32_t>(4 * n * k), f.out(reinterpret_cast<BcDemuxResult*>(out), n),
+          all_out ? f.out(reinterpret_cast<BcResult*>(all_out), n * k) : Piece<BcResult>{}};
 }
 
-// search + choice over basecalls that are on the device, and the copies of the results to the caller; x (demux_args)
-// outlives the call's StreamDrain
-int enqueue_demux(lva_decoder* d, const Arena& a, const Calls& c, const DemuxSet& s, int32_t n_reads, const DemuxArgs& x,
-                  lva_demux_pos* out, lva_payload_pos* all_out) {
-  static_assert(sizeof(lva_demux_pos) == sizeof(BcDemuxResult), "lva_demux_pos layout");
-  const size_t n = (size_t)n_reads, k = x.pats.size();
-  HIP_TRY(hipMemcpyAsync(a.ptr(s.pats), x.pats.data(), sizeof(BcPatterns) * k, hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(hipMemcpyAsync(a.ptr(s.min_len), x.min_len.data(), 4 * k, hipMemcpyHostToDevice, d->stream));
-  int e = launch_bc_search_multi(a.ptr(c.bases), a.ptr(c.off), a.ptr(c.nb), n_reads, a.ptr(s.pats), (int32_t)k, a.ptr(s.best), d->stream);
-  if (!e) e = launch_bc_demux_finalize(a.ptr(c.trans), a.ptr(c.off), a.ptr(c.nb), n_reads, a.ptr(s.pats), a.ptr(s.min_len), (int32_t)k,
-                                       x.max_dist, x.min_margin, a.ptr(s.best), a.ptr(s.res), a.ptr(s.all), d->stream);
-  if (e) return launch_status(e);
-  HIP_TRY(hipMemcpyAsync(out, a.ptr(s.res), sizeof(BcDemuxResult) * n, hipMemcpyDeviceToHost, d->stream));
-  if (all_out) HIP_TRY(hipMemcpyAsync(all_out, a.ptr(s.all), sizeof(BcResult) * n * k, hipMemcpyDeviceToHost, d->stream));
-  return LVA_OK;
+// search + choice over basecalls that are on the device
+int enqueue_demux(const Frame& f, const Calls& c, const DemuxSet& s, int32_t n_reads, const DemuxArgs& x) {
+  const int32_t k = (int32_t)x.pats.size();
+  int e = launch_bc_search_multi(c.bases, c.off, c.nb, n_reads, s.pats, k, s.best, f.stream());
+  if (!e) e = launch_bc_demux_finalize(c.trans, c.off, c.nb, n_reads, s.pats, s.min_len, k, x.max_dist, x.min_margin, s.best, s.res, s.all,
+                                       f.stream());
+  return launch_status(e);
 }
 
 // lva_demux_batch (post on the host) and lva_demux_batch_device: basecall, then search + choice
@@ -385,16 +407,14 @@ int demux_stage(lva_decoder* d, const float* post, bool post_on_host, const int6
   size_t T = 0;
   int st = stage_enter(d, row_offsets, n, &T);
   if (st != kRun) return st;
-  Arena arena;
-  HostPost hp;
-  const Calls bc = basecall_set(arena, (size_t)n, T);
-  const DemuxSet dm = demux_set(arena, (size_t)n, x.pats.size(), all_out != nullptr);
-  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
-  StreamDrain drain(d->stream);
-  if (post_on_host && (st = upload_post(d, post, T, &hp)) != LVA_OK) return st;
-  if ((st = enqueue_basecall(d, arena, bc, post_on_host ? hp.dev : post, row_offsets, n)) != LVA_OK) return st;
-  if ((st = enqueue_demux(d, arena, bc, dm, n, x, out, all_out)) != LVA_OK) return st;
-  return drain.finish();
+  Frame f(d->stream);
+  const Piece<float> up = post_on_host ? f.in(post, kPostRow * T) : Piece<float>{};
+  const Calls bc = basecall_set(f, row_offsets, (size_t)n, T, nullptr, nullptr, nullptr);
+  const DemuxSet dm = demux_set(f, (size_t)n, x, out, all_out);
+  if ((st = f.begin()) != LVA_OK) return st;
+  if ((st = enqueue_basecall(f, bc, post_on_host ? up.ptr() : post, n)) != LVA_OK) return st;
+  if ((st = enqueue_demux(f, bc, dm, n, x)) != LVA_OK) return st;
+  return f.finish();
 }
 
 }  // namespace
@@ -423,37 +443,22 @@ int lva_demux_bases_batch(lva_decoder* d, const char* bases, const uint32_t* tra
   int st = stage_enter(d, base_offsets, n_reads, &T);
   if (st != kRun) return st;
   const std::vector<int32_t> nb = read_lengths(base_offsets, n_reads);
-  Arena arena;
-  const Calls calls = given_set(arena, nb.size(), T);
-  const DemuxSet dm = demux_set(arena, nb.size(), x.pats.size(), all_out != nullptr);
-  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
-  StreamDrain drain(d->stream);
-  if ((st = enqueue_given(d, arena, calls, bases, trans, base_offsets, nb, T)) != LVA_OK) return st;
-  if ((st = enqueue_demux(d, arena, calls, dm, n_reads, x, out, all_out)) != LVA_OK) return st;
-  return drain.finish();
+  Frame f(d->stream);
+  const Calls calls = given_set(f, bases, trans, base_offsets, nb, T);
+  const DemuxSet dm = demux_set(f, nb.size(), x, out, all_out);
+  if ((st = f.begin()) != LVA_OK) return st;
+  if ((st = enqueue_demux(f, calls, dm, n_reads, x)) != LVA_OK) return st;
+  return f.finish();
 }
 
 }  // extern "C"
 
 /* ---------------------------------------------------------------------------------------------
  * the consumers of a decoded list (csrc/ls_kernels.hip).  Like the RS entry
- * points they take a device ordinal, work on a stream of their own and leave every decoder's profile alone.
- * Arguments first, then the device ordinal.
+ * points they take a device ordinal, work on a stream of their own (Frame::open) and leave every decoder's profile
+ * alone.  Arguments first, then the device ordinal.
  * ------------------------------------------------------------------------------------------- */
 namespace {
-
-struct LsStream {               // a stream for the length of one call
-  hipStream_t s = nullptr;
-  ~LsStream() { if (s) (void)hipStreamDestroy(s); }
-};
-
-int ls_open(int32_t device, LsStream* st) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return LVA_ERR_NO_DEVICE;
-  if (hipSetDevice(device) != hipSuccess) return LVA_ERR_NO_DEVICE;
-  HIP_TRY(hipStreamCreateWithFlags(&st->s, hipStreamNonBlocking));
-  return LVA_OK;
-}
 
 // msgs / counts of n reads: the shape every list consumer accepts
 bool ls_shape_ok(int32_t n_reads, int32_t list_size, uint32_t msg_len) {
@@ -474,24 +479,17 @@ int lva_list_filter(int32_t device, const uint8_t* msgs, const int32_t* counts, 
   if ((uint64_t)msg_len != 12ull + 8ull + 8ull * (uint64_t)bytes_per_oligo + (pad ? 1ull : 0ull)) return LVA_ERR_ARG;
   if (n_reads == 0) return LVA_OK;
   const int32_t use = use_entries ? use_entries : list_size;
-  LsStream st;
-  if (const int so = ls_open(device, &st)) return so;
-  const size_t n = (size_t)n_reads, mb = n * (size_t)list_size * msg_len, pb = n * (size_t)bytes_per_oligo;
-  Arena arena;
-  const auto d_msgs = arena.add<uint8_t>(mb);            // 256-byte aligned and padded: whole dwords may be read
-  const auto d_counts = arena.add<int32_t>(n), d_index = arena.add<int32_t>(n), d_rank = arena.add<int32_t>(n);
-  const auto d_pay = arena.add<uint8_t>(pb);
-  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
-  StreamDrain drain(st.s);
-  HIP_TRY(hipMemcpyAsync(arena.ptr(d_msgs), msgs, mb, hipMemcpyHostToDevice, st.s));
-  HIP_TRY(hipMemcpyAsync(arena.ptr(d_counts), counts, 4 * n, hipMemcpyHostToDevice, st.s));
-  const int e = launch_ls_filter(arena.ptr(d_msgs), arena.ptr(d_counts), n_reads, list_size, msg_len, use, bytes_per_oligo, num_oligos,
-                                 pad, arena.ptr(d_index), arena.ptr(d_rank), arena.ptr(d_pay), st.s);
-  if (e) return launch_status(e);
-  HIP_TRY(hipMemcpyAsync(out_index, arena.ptr(d_index), 4 * n, hipMemcpyDeviceToHost, st.s));
-  HIP_TRY(hipMemcpyAsync(out_rank, arena.ptr(d_rank), 4 * n, hipMemcpyDeviceToHost, st.s));
-  HIP_TRY(hipMemcpyAsync(out_payload, arena.ptr(d_pay), pb, hipMemcpyDeviceToHost, st.s));
-  return drain.finish();
+  Frame f;
+  if (const int so = f.open(device)) return so;
+  const size_t n = (size_t)n_reads;
+  const auto d_msgs = f.in(msgs, n * (size_t)list_size * msg_len);     // 256-byte aligned and padded: whole dwords may be read
+  const auto d_counts = f.in(counts, n);
+  const auto d_index = f.out(out_index, n), d_rank = f.out(out_rank, n);
+  const auto d_pay = f.out(out_payload, n * (size_t)bytes_per_oligo);
+  if (const int st = f.begin()) return st;
+  const int e = launch_ls_filter(d_msgs, d_counts, n_reads, list_size, msg_len, use, bytes_per_oligo, num_oligos, pad, d_index, d_rank,
+                                 d_pay, f.stream());
+  return e ? launch_status(e) : f.finish();
 }
 
 int lva_list_consensus(int32_t device, const int32_t* index, const uint8_t* payload, int32_t n_reads, int32_t bytes_per_oligo,
@@ -502,27 +500,19 @@ int lva_list_consensus(int32_t device, const int32_t* index, const uint8_t* payl
   for (int32_t i = 0; i < n_reads; ++i)
     if (index[i] >= num_oligos) return LVA_ERR_ARG;      // (negative: the read passed no entry and has no vote)
   if (n_reads == 0) return LVA_OK;
-  LsStream st;
-  if (const int so = ls_open(device, &st)) return so;
-  const size_t n = (size_t)n_reads, no = (size_t)num_oligos, pb = n * (size_t)bytes_per_oligo, ob = no * (size_t)bytes_per_oligo;
-  Arena arena;
-  const auto d_index = arena.add<int32_t>(n), d_order = arena.add<int32_t>(n);
-  const auto d_pay = arena.add<uint8_t>(pb);
-  const auto d_bucket = arena.add<int32_t>(no + 1);
-  const auto d_present = arena.add<uint8_t>(no), d_out = arena.add<uint8_t>(ob);
-  const auto d_votes = arena.add<int32_t>(no);
-  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
-  StreamDrain drain(st.s);
-  HIP_TRY(hipMemcpyAsync(arena.ptr(d_index), index, 4 * n, hipMemcpyHostToDevice, st.s));
-  HIP_TRY(hipMemcpyAsync(arena.ptr(d_pay), payload, pb, hipMemcpyHostToDevice, st.s));
-  const int e = launch_ls_consensus(arena.ptr(d_index), arena.ptr(d_pay), n_reads, bytes_per_oligo, num_oligos, first_only ? 1 : 0,
-                                    arena.ptr(d_bucket), arena.ptr(d_order), arena.ptr(d_present), arena.ptr(d_out),
-                                    arena.ptr(d_votes), st.s);
-  if (e) return launch_status(e);
-  HIP_TRY(hipMemcpyAsync(out_present, arena.ptr(d_present), no, hipMemcpyDeviceToHost, st.s));
-  HIP_TRY(hipMemcpyAsync(out_payload, arena.ptr(d_out), ob, hipMemcpyDeviceToHost, st.s));
-  HIP_TRY(hipMemcpyAsync(out_votes, arena.ptr(d_votes), 4 * no, hipMemcpyDeviceToHost, st.s));
-  return drain.finish();
+  Frame f;
+  if (const int so = f.open(device)) return so;
+  const size_t n = (size_t)n_reads, no = (size_t)num_oligos;
+  const auto d_index = f.in(index, n);
+  const auto d_order = f.scratch<int32_t>(n);
+  const auto d_pay = f.in(payload, n * (size_t)bytes_per_oligo);
+  const auto d_bucket = f.scratch<int32_t>(no + 1);
+  const auto d_present = f.out(out_present, no), d_out = f.out(out_payload, no * (size_t)bytes_per_oligo);
+  const auto d_votes = f.out(out_votes, no);
+  if (const int st = f.begin()) return st;
+  const int e = launch_ls_consensus(d_index, d_pay, n_reads, bytes_per_oligo, num_oligos, first_only ? 1 : 0, d_bucket, d_order, d_present,
+                                    d_out, d_votes, f.stream());
+  return e ? launch_status(e) : f.finish();
 }
 
 int lva_list_stats(int32_t device, const uint8_t* msgs, const int32_t* counts, const uint8_t* truth, int32_t n_reads,
@@ -531,25 +521,90 @@ int lva_list_stats(int32_t device, const uint8_t* msgs, const int32_t* counts, c
   if (!msgs || !counts || !truth || !out) return LVA_ERR_ARG;
   if (!ls_shape_ok(n_reads, list_size, msg_len)) return LVA_ERR_ARG;
   if (n_reads == 0) return LVA_OK;
-  LsStream st;
-  if (const int so = ls_open(device, &st)) return so;
-  const size_t n = (size_t)n_reads, mb = n * (size_t)list_size * msg_len, tb = n * msg_len;
-  Arena arena;
-  const auto d_msgs = arena.add<uint8_t>(mb);
-  const auto d_counts = arena.add<int32_t>(n);
-  const auto d_truth = arena.add<uint8_t>(tb);
-  const auto d_packed = arena.add<uint64_t>(kLsPackWords * n);
-  const auto d_out = arena.add<int32_t>(kLsStatFields * n);
-  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
-  StreamDrain drain(st.s);
-  HIP_TRY(hipMemcpyAsync(arena.ptr(d_msgs), msgs, mb, hipMemcpyHostToDevice, st.s));
-  HIP_TRY(hipMemcpyAsync(arena.ptr(d_counts), counts, 4 * n, hipMemcpyHostToDevice, st.s));
-  HIP_TRY(hipMemcpyAsync(arena.ptr(d_truth), truth, tb, hipMemcpyHostToDevice, st.s));
-  const int e = launch_ls_stats(arena.ptr(d_msgs), arena.ptr(d_counts), arena.ptr(d_truth), n_reads, list_size, msg_len,
-                                arena.ptr(d_packed), arena.ptr(d_out), st.s);
-  if (e) return launch_status(e);
-  HIP_TRY(hipMemcpyAsync(out, arena.ptr(d_out), 4 * kLsStatFields * n, hipMemcpyDeviceToHost, st.s));
-  return drain.finish();
+  Frame f;
+  if (const int so = f.open(device)) return so;
+  const size_t n = (size_t)n_reads;
+  const auto d_msgs = f.in(msgs, n * (size_t)list_size * msg_len);
+  const auto d_counts = f.in(counts, n);
+  const auto d_truth = f.in(truth, n * msg_len);
+  const auto d_packed = f.scratch<uint64_t>(kLsPackWords * n);
+  const auto d_out = f.out(reinterpret_cast<int32_t*>(out), kLsStatFields * n);
+  if (const int st = f.begin()) return st;
+  const int e = launch_ls_stats(d_msgs, d_counts, d_truth, n_reads, list_size, msg_len, d_packed, d_out, f.stream());
+  return e ? launch_status(e) : f.finish();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// the Reed-Solomon outer code (csrc/rs_kernels.hip).  A device ordinal, a stream of its
+// own, complete on return; lva_rs_last_error is the text of the calling thread's last failed RS call.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+thread_local std::string g_rs_error;
+
+bool rs_shape_ok(int n_cw, int n_total, int fec) { return n_cw >= 0 && fec >= 1 && fec <= kRsMaxFec && n_total > fec && n_total <= kRsN; }
+
+// n_cw > 0 codewords of n_total symbols -> their first n_out decoded symbols; ok may be null (its piece is still written)
+int rs_run(int32_t device, const uint16_t* symbols, int32_t n_cw, int32_t n_total, int32_t fec, const int32_t* erasures, int32_t n_er,
+           uint16_t pad_sym, uint16_t fail_sym, uint16_t* out, int32_t n_out, int32_t* ok) {
+  std::vector<uint16_t> gexp, glog;
+  Frame f;
+  if (const int so = f.open(device)) return so;
+  tr_gf_tables(&gexp, &glog);
+  const auto d_sym = f.in(symbols, (size_t)n_cw * n_total);
+  const auto d_out = f.out(out, (size_t)n_cw * n_out);
+  const auto d_gexp = f.in(gexp.data(), gexp.size()), d_glog = f.in(glog.data(), glog.size());
+  const auto d_er = f.in(erasures, (size_t)n_er);
+  const auto d_ok = f.out(ok, (size_t)n_cw);
+  int st = f.begin();
+  if (st == LVA_OK)
+    st = launch_status(launch_rs_decode(d_sym, n_cw, n_total, fec, d_er, n_er, pad_sym, fail_sym, d_gexp, d_glog, d_out, n_out, d_ok,
+                                        f.stream()));
+  if (st == LVA_OK) st = f.finish();
+  if (st == LVA_ERR_HIP) g_rs_error = lva_last_hip_error();
+  return st;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* lva_rs_last_error(void) { return g_rs_error.c_str(); }
+
+int lva_rs_decode(int32_t device, const uint16_t* symbols, int32_t n_codewords, int32_t n_total, int32_t redundancy,
+                  const int32_t* erasures, int32_t n_erasures, uint16_t pad_symbol, uint16_t fail_symbol, uint16_t* out,
+                  int32_t* ok) {
+  if (!rs_shape_ok(n_codewords, n_total, redundancy)) return LVA_ERR_ARG;
+  if (n_erasures < 0 || (n_codewords > 0 && (!symbols || !out)) || (n_erasures > 0 && !erasures)) return LVA_ERR_ARG;
+  std::vector<uint8_t> seen((size_t)n_total, 0);             // "erasure positions must be unique and inside the block" (:213-218)
+  for (int i = 0; i < n_erasures; ++i) {
+    if (erasures[i] < 0 || erasures[i] >= n_total || seen[(size_t)erasures[i]]) return LVA_ERR_ARG;
+    seen[(size_t)erasures[i]] = 1;
+  }
+  if (n_codewords == 0) return LVA_OK;
+  return rs_run(device, symbols, n_codewords, n_total, redundancy, erasures, n_erasures, pad_symbol, fail_symbol, out,
+                n_total - redundancy, ok);
+}
+
+int lva_rs_encode(int32_t device, const uint16_t* data, int32_t n_codewords, int32_t n_data, int32_t redundancy,
+                  uint16_t pad_symbol, uint16_t* out) {
+  if (n_data < 1) return LVA_ERR_ARG;
+  const int n_total = n_data + redundancy;
+  if (!rs_shape_ok(n_codewords, n_total, redundancy)) return LVA_ERR_ARG;
+  if (n_codewords > 0 && (!data || !out)) return LVA_ERR_ARG;
+  if (n_codewords == 0) return LVA_OK;
+  // systematic encoding = filling in the parity symbols as erasures: the unique codeword with these data symbols
+  std::vector<uint16_t> rx((size_t)n_codewords * n_total, 0);
+  for (int c = 0; c < n_codewords; ++c) std::memcpy(&rx[(size_t)c * n_total], data + (size_t)c * n_data, (size_t)n_data * 2);
+  std::vector<int32_t> er((size_t)redundancy), ok((size_t)n_codewords, 0);
+  for (int i = 0; i < redundancy; ++i) er[(size_t)i] = n_data + i;
+  const int rc = rs_run(device, rx.data(), n_codewords, n_total, redundancy, er.data(), redundancy, pad_symbol, 0, out, n_total, ok.data());
+  if (rc != LVA_OK) return rc;
+  for (int c = 0; c < n_codewords; ++c)
+    if (!ok[(size_t)c]) { g_rs_error = "encode: the erasure decode of the parity symbols failed"; return LVA_ERR_HIP; }
+  return LVA_OK;
 }
 
 }  // extern "C"
@@ -603,7 +658,7 @@ int lva_rs_trials(int32_t device, const int32_t* index, const uint8_t* payload, 
   sh.n_reads = n_reads; sh.bpo = bytes_per_oligo; sh.num_oligos = num_oligos; sh.fec = redundancy; sh.n_points = n_points;
   sh.k0 = (uint32_t)seed; sh.k1 = (uint32_t)(seed >> 32);
   std::copy(reads_to_use, reads_to_use + n_points, sh.points);
-  std::vector<uint16_t> gexp, glog, truth(s * nd, 0);    // (these outlive the call's StreamDrain)
+  std::vector<uint16_t> gexp, glog, truth(s * nd, 0);    // (these outlive the call's frame)
   tr_gf_tables(&gexp, &glog);
   for (size_t c = 0; c < s; ++c)                         // column c of the original file, as the decoder's output is laid out
     for (size_t j = 0; j < nd; ++j) {
@@ -611,51 +666,41 @@ int lva_rs_trials(int32_t device, const int32_t* index, const uint8_t* payload, 
       const uint32_t lo = at < original_bytes ? original[at] : 0u, hi = at + 1 < original_bytes ? original[at + 1] : 0u;
       truth[c * nd + j] = (uint16_t)(lo | (hi << 8));
     }
-  LsStream st;
-  if (const int so = ls_open(device, &st)) return so;
-  Arena arena;
-  const auto d_index = arena.add<int32_t>(n), d_order = arena.add<int32_t>(n);
-  const auto d_pay = arena.add<uint8_t>(n * bpo);
-  const auto d_bucket = arena.add<int32_t>(no + 1);
-  const auto d_gexp = arena.add<uint16_t>(kTrGexpWords), d_glog = arena.add<uint16_t>(kTrGlogWords), d_truth = arena.add<uint16_t>(s * nd);
-  const auto d_stats = arena.add<int32_t>(4 * K * T);
-  const auto d_place = arena.add<int32_t>(chunk * n), d_cnt = arena.add<int32_t>(chunk * n);
-  const auto d_nmem = arena.add<int32_t>(K * chunk * no), d_erl = arena.add<int32_t>(K * chunk * no);
-  const auto d_ern = arena.add<int32_t>(K * chunk), d_pp = arena.add<int32_t>(2 * K * chunk), d_okeq = arena.add<int32_t>(2 * K * chunk * s);
-  const auto d_sym = arena.add<uint16_t>(K * chunk * s * no), d_dec = arena.add<uint16_t>(K * chunk * s * nd);
-  const auto d_cons = out_payload ? arena.add<uint8_t>(K * chunk * no * bpo) : Arena::Piece<uint8_t>{};
-  const auto d_pres = out_present ? arena.add<uint8_t>(K * chunk * no) : Arena::Piece<uint8_t>{};
-  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
-  StreamDrain drain(st.s);
-  HIP_TRY(hipMemcpyAsync(arena.ptr(d_index), index, 4 * n, hipMemcpyHostToDevice, st.s));
-  HIP_TRY(hipMemcpyAsync(arena.ptr(d_pay), payload, n * bpo, hipMemcpyHostToDevice, st.s));
-  HIP_TRY(hipMemcpyAsync(arena.ptr(d_gexp), gexp.data(), 2 * kTrGexpWords, hipMemcpyHostToDevice, st.s));
-  HIP_TRY(hipMemcpyAsync(arena.ptr(d_glog), glog.data(), 2 * kTrGlogWords, hipMemcpyHostToDevice, st.s));
-  HIP_TRY(hipMemcpyAsync(arena.ptr(d_truth), truth.data(), 2 * s * nd, hipMemcpyHostToDevice, st.s));
-  int e = launch_ls_bucket_scan(arena.ptr(d_index), n_reads, num_oligos, arena.ptr(d_bucket), st.s);
-  if (!e) e = launch_tr_bucket_list(arena.ptr(d_index), n_reads, num_oligos, arena.ptr(d_bucket), arena.ptr(d_order), st.s);
+  Frame f;
+  if (const int so = f.open(device)) return so;
+  const auto d_index = f.in(index, n);
+  const auto d_order = f.scratch<int32_t>(n);
+  const auto d_pay = f.in(payload, n * bpo);
+  const auto d_bucket = f.scratch<int32_t>(no + 1);
+  const auto d_gexp = f.in(gexp.data(), kTrGexpWords), d_glog = f.in(glog.data(), kTrGlogWords), d_truth = f.in(truth.data(), s * nd);
+  const auto d_stats = f.out(out_stats, 4 * K * T);
+  const auto d_place = f.scratch<int32_t>(chunk * n), d_cnt = f.scratch<int32_t>(chunk * n);
+  const auto d_nmem = f.scratch<int32_t>(K * chunk * no), d_erl = f.scratch<int32_t>(K * chunk * no);
+  const auto d_ern = f.scratch<int32_t>(K * chunk), d_pp = f.scratch<int32_t>(2 * K * chunk), d_okeq = f.scratch<int32_t>(2 * K * chunk * s);
+  const auto d_sym = f.scratch<uint16_t>(K * chunk * s * no), d_dec = f.scratch<uint16_t>(K * chunk * s * nd);
+  const auto d_cons = out_payload ? f.scratch<uint8_t>(K * chunk * no * bpo) : Piece<uint8_t>{};     // copied out chunk by chunk, below
+  const auto d_pres = out_present ? f.scratch<uint8_t>(K * chunk * no) : Piece<uint8_t>{};
+  int st = f.begin();
+  if (st != LVA_OK) return st;
+  int e = launch_ls_bucket_scan(d_index, n_reads, num_oligos, d_bucket, f.stream());
+  if (!e) e = launch_tr_bucket_list(d_index, n_reads, num_oligos, d_bucket, d_order, f.stream());
   if (e) return launch_status(e);
   for (size_t at = 0; at < T; at += chunk) {             // a trial depends on (seed, trial number) alone: chunks change nothing
     const size_t c = std::min(chunk, T - at);
     sh.chunk = (int32_t)c;
     sh.first_trial = first_trial + (uint32_t)at;
-    e = launch_tr_consensus(sh, arena.ptr(d_bucket), arena.ptr(d_order), arena.ptr(d_pay), arena.ptr(d_place), arena.ptr(d_cnt),
-                            arena.ptr(d_nmem), arena.ptr(d_sym), arena.ptr(d_cons), st.s);
-    if (!e) e = launch_tr_erasures(sh, arena.ptr(d_nmem), arena.ptr(d_erl), arena.ptr(d_ern), arena.ptr(d_pp), arena.ptr(d_pres), st.s);
-    if (!e) e = launch_tr_decode(sh, arena.ptr(d_sym), arena.ptr(d_erl), arena.ptr(d_ern), arena.ptr(d_gexp), arena.ptr(d_glog),
-                                 arena.ptr(d_dec), arena.ptr(d_truth), original_bytes, arena.ptr(d_okeq), st.s);
-    if (!e) e = launch_tr_fold(sh, arena.ptr(d_okeq), arena.ptr(d_pp), arena.ptr(d_stats), n_trials, (int32_t)at, st.s);
+    e = launch_tr_consensus(sh, d_bucket, d_order, d_pay, d_place, d_cnt, d_nmem, d_sym, d_cons, f.stream());
+    if (!e) e = launch_tr_erasures(sh, d_nmem, d_erl, d_ern, d_pp, d_pres, f.stream());
+    if (!e) e = launch_tr_decode(sh, d_sym, d_erl, d_ern, d_gexp, d_glog, d_dec, d_truth, original_bytes, d_okeq, f.stream());
+    if (!e) e = launch_tr_fold(sh, d_okeq, d_pp, d_stats, n_trials, (int32_t)at, f.stream());
     if (e) return launch_status(e);
     for (size_t k = 0; k < K; ++k) {                     // the chunk holds [point][trial of the chunk], the caller [point][trial]
-      if (out_present)
-        HIP_TRY(hipMemcpyAsync(out_present + (k * T + at) * no, arena.ptr(d_pres) + k * c * no, c * no, hipMemcpyDeviceToHost, st.s));
-      if (out_payload)
-        HIP_TRY(hipMemcpyAsync(out_payload + (k * T + at) * no * bpo, arena.ptr(d_cons) + k * c * no * bpo, c * no * bpo,
-                               hipMemcpyDeviceToHost, st.s));
+      if (out_present && (st = f.download(out_present + (k * T + at) * no, d_pres, k * c * no, c * no)) != LVA_OK) return st;
+      if (out_payload && (st = f.download(out_payload + (k * T + at) * no * bpo, d_cons, k * c * no * bpo, c * no * bpo)) != LVA_OK)
+        return st;
     }
   }
-  HIP_TRY(hipMemcpyAsync(out_stats, arena.ptr(d_stats), 16 * K * T, hipMemcpyDeviceToHost, st.s));
-  return drain.finish();
+  return f.finish();
 }
 
 }  // extern "C"
@@ -742,39 +787,32 @@ int sim_barcodes(const char* start_bc, const char* end_bc, uint32_t flank_lo, ui
 }
 
 struct SimTables {
-  Arena::Piece<uint16_t> posinfo;
-  Arena::Piece<uint32_t> cdf;
-  Arena::Piece<uint8_t> bc;
-  Arena::Piece<uint8_t> pool;             // with a pool only: its messages, its table if it has one, and per read what was drawn
-  Arena::Piece<uint32_t> pool_cdf;
-  Arena::Piece<int32_t> source;
-  Arena::Piece<uint8_t> rc;
+  Piece<uint16_t> posinfo;
+  Piece<uint32_t> cdf;
+  Piece<uint8_t> bc;
+  Piece<uint8_t> pool;             // with a pool only: its messages, its table if it has one, and per read what was drawn
+  Piece<uint32_t> pool_cdf;
+  Piece<int32_t> source;
+  Piece<uint8_t> rc;
+  uint32_t n_pool;
+  SimPool dev() const {            // the pool as the kernel takes it, once the frame has begun
+    SimPool p;
+    p.msgs = pool; p.cdf = pool_cdf; p.n = n_pool; p.source = source; p.rc = rc;
+    return p;
+  }
 };
-SimTables sim_tables(Arena& a, const SimCall& c, const SimPoolHost* pool, size_t n_reads) {
-  SimTables t{a.add<uint16_t>(c.posinfo.size()), a.add<uint32_t>(c.p.dwell_k), a.add<uint8_t>(sizeof c.bc), {}, {}, {}, {}};
+// c, dwell_cdf and the pool are declared before the frame; source_out, rc_out: what was drawn, to the caller (null: not wanted)
+SimTables sim_tables(Frame& f, const SimCall& c, const uint32_t* dwell_cdf, const SimPoolHost* pool, size_t n_reads,
+                     int32_t* source_out, uint8_t* rc_out) {
+  SimTables t{f.in(c.posinfo.data(), c.posinfo.size()), f.in(dwell_cdf, c.p.dwell_k), f.in(c.bc, sizeof c.bc), {}, {}, {}, {}, 0};
   if (pool) {
-    t.pool = a.add<uint8_t>((size_t)pool->n * c.p.msg_len);
-    if (pool->cdf) t.pool_cdf = a.add<uint32_t>((size_t)pool->n);
-    t.source = a.add<int32_t>(n_reads);
-    t.rc = a.add<uint8_t>(n_reads);
+    t.pool = f.in(pool->msgs, (size_t)pool->n * c.p.msg_len);
+    if (pool->cdf) t.pool_cdf = f.in(pool->cdf, (size_t)pool->n);
+    t.source = f.out(source_out, n_reads);
+    t.rc = f.out(rc_out, n_reads);
+    t.n_pool = (uint32_t)pool->n;
   }
   return t;
-}
-// c, dwell_cdf and the pool outlive the call's StreamDrain.  *dev: the pool as the kernel takes it (pool == null: untouched)
-int upload_sim_tables(lva_decoder* d, const Arena& a, const SimTables& t, const SimCall& c, const uint32_t* dwell_cdf,
-                      const SimPoolHost* pool, SimPool* dev) {
-  HIP_TRY(hipMemcpyAsync(a.ptr(t.posinfo), c.posinfo.data(), 2 * c.posinfo.size(), hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(hipMemcpyAsync(a.ptr(t.cdf), dwell_cdf, 4 * (size_t)c.p.dwell_k, hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(hipMemcpyAsync(a.ptr(t.bc), c.bc, sizeof c.bc, hipMemcpyHostToDevice, d->stream));
-  if (!pool) return LVA_OK;
-  HIP_TRY(hipMemcpyAsync(a.ptr(t.pool), pool->msgs, (size_t)pool->n * c.p.msg_len, hipMemcpyHostToDevice, d->stream));
-  if (pool->cdf) HIP_TRY(hipMemcpyAsync(a.ptr(t.pool_cdf), pool->cdf, 4 * (size_t)pool->n, hipMemcpyHostToDevice, d->stream));
-  dev->msgs = a.ptr(t.pool);
-  dev->cdf = a.ptr(t.pool_cdf);
-  dev->n = (uint32_t)pool->n;
-  dev->source = a.ptr(t.source);
-  dev->rc = a.ptr(t.rc);
-  return LVA_OK;
 }
 
 // the one body of lva_simulate_plan and lva_simulate_pool_plan (pool == null: the former)
@@ -792,19 +830,15 @@ int simulate_plan(lva_decoder* d, uint64_t seed, uint32_t first_read, int32_t n_
   if (st != kRun) return st;
   const size_t n = (size_t)n_reads;
   std::vector<int32_t> lens(2 * n);
-  Arena arena;
-  const SimTables tab = sim_tables(arena, c, pool, n);
-  const auto d_lens = arena.add<int32_t>(2 * n);
-  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
-  StreamDrain drain(d->stream);
-  SimPool dpool;
-  if ((st = upload_sim_tables(d, arena, tab, c, dwell_cdf, pool, &dpool)) != LVA_OK) return st;
-  const int e = launch_sim_strand(c.p, pool ? &dpool : nullptr, n_reads, arena.ptr(tab.posinfo), arena.ptr(tab.cdf),
-                                  arena.ptr(tab.bc), nullptr, nullptr, arena.ptr(d_lens), nullptr, nullptr, nullptr, nullptr,
-                                  d->stream);
+  Frame f(d->stream);
+  const SimTables tab = sim_tables(f, c, dwell_cdf, pool, n, nullptr, nullptr);
+  const auto d_lens = f.out(lens.data(), 2 * n);
+  if ((st = f.begin()) != LVA_OK) return st;
+  const SimPool dpool = tab.dev();
+  const int e = launch_sim_strand(c.p, pool ? &dpool : nullptr, n_reads, tab.posinfo, tab.cdf, tab.bc, nullptr, nullptr, d_lens, nullptr,
+                                  nullptr, nullptr, nullptr, f.stream());
   if (e) return launch_status(e);
-  HIP_TRY(hipMemcpyAsync(lens.data(), arena.ptr(d_lens), 8 * n, hipMemcpyDeviceToHost, d->stream));
-  if ((st = drain.finish()) != LVA_OK) return st;
+  if ((st = f.finish()) != LVA_OK) return st;
   row_offsets_out[0] = base_offsets_out[0] = 0;
   for (size_t i = 0; i < n; ++i) {
     base_offsets_out[i + 1] = base_offsets_out[i] + lens[2 * i];
@@ -833,33 +867,21 @@ int simulate_fill(lva_decoder* d, uint64_t seed, uint32_t first_read, int32_t n_
   if (st != kRun) return st;
   const size_t n = (size_t)n_reads, mb = n * c.p.msg_len;
   int32_t bad = 0;
-  Arena arena;
-  const SimTables tab = sim_tables(arena, c, pool, n);
-  const auto d_row = arena.add<int64_t>(n + 1), d_base = arena.add<int64_t>(n + 1);
-  const auto d_msgs = arena.add<uint8_t>(mb), d_bases = arena.add<uint8_t>(B), d_tidx = arena.add<uint8_t>(T);
-  const auto d_bad = arena.add<int32_t>(1);
-  if (arena.alloc() != LVA_OK) return LVA_ERR_NOMEM;
-  StreamDrain drain(d->stream);
-  SimPool dpool;
-  if ((st = upload_sim_tables(d, arena, tab, c, dwell_cdf, pool, &dpool)) != LVA_OK) return st;
-  HIP_TRY(hipMemcpyAsync(arena.ptr(d_row), row_offsets, 8 * (n + 1), hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(hipMemcpyAsync(arena.ptr(d_base), base_offsets, 8 * (n + 1), hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(hipMemsetAsync(arena.ptr(d_bad), 0, sizeof(int32_t), d->stream));
-  int e = launch_sim_strand(c.p, pool ? &dpool : nullptr, n_reads, arena.ptr(tab.posinfo), arena.ptr(tab.cdf), arena.ptr(tab.bc),
-                            arena.ptr(d_row), arena.ptr(d_base), nullptr, arena.ptr(d_msgs), arena.ptr(d_bases), arena.ptr(d_tidx),
-                            arena.ptr(d_bad), d->stream);
+  Frame f(d->stream);
+  const SimTables tab = sim_tables(f, c, dwell_cdf, pool, n, source_out, rc_out);
+  const auto d_row = f.in(row_offsets, n + 1), d_base = f.in(base_offsets, n + 1);
+  const auto d_msgs = f.out(msgs_out, mb), d_bases = f.out(bases_out, B), d_tidx = f.out(true_idx_out, T);
+  const auto d_bad = f.inout(&bad, &bad, 1);             // goes up as 0, comes back as what the strand kernel found
+  if ((st = f.begin()) != LVA_OK) return st;
+  const SimPool dpool = tab.dev();
+  int e = launch_sim_strand(c.p, pool ? &dpool : nullptr, n_reads, tab.posinfo, tab.cdf, tab.bc, d_row, d_base, nullptr, d_msgs, d_bases,
+                            d_tidx, d_bad, f.stream());
   if (e) return launch_status(e);
   HIP_TRY(hipEventRecord(d->ev_total0, d->stream));
-  e = launch_sim_scores(c.p, n_reads, arena.ptr(d_row), (uint32_t)T, arena.ptr(d_tidx), scale, margin, clip, scores_dev, d->stream);
+  e = launch_sim_scores(c.p, n_reads, d_row, (uint32_t)T, d_tidx, scale, margin, clip, scores_dev, f.stream());
   if (e) return launch_status(e);
   HIP_TRY(hipEventRecord(d->ev_total1, d->stream));
-  HIP_TRY(hipMemcpyAsync(msgs_out, arena.ptr(d_msgs), mb, hipMemcpyDeviceToHost, d->stream));
-  if (bases_out && B) HIP_TRY(hipMemcpyAsync(bases_out, arena.ptr(d_bases), B, hipMemcpyDeviceToHost, d->stream));
-  if (true_idx_out && T) HIP_TRY(hipMemcpyAsync(true_idx_out, arena.ptr(d_tidx), T, hipMemcpyDeviceToHost, d->stream));
-  if (pool && source_out) HIP_TRY(hipMemcpyAsync(source_out, arena.ptr(tab.source), 4 * n, hipMemcpyDeviceToHost, d->stream));
-  if (pool && rc_out) HIP_TRY(hipMemcpyAsync(rc_out, arena.ptr(tab.rc), n, hipMemcpyDeviceToHost, d->stream));
-  HIP_TRY(hipMemcpyAsync(&bad, arena.ptr(d_bad), sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
-  if ((st = drain.finish()) != LVA_OK) return st;
+  if ((st = f.finish()) != LVA_OK) return st;
   if ((st = tp_profile(d, T, true)) != LVA_OK) return st;
   return bad ? LVA_ERR_ARG : LVA_OK;           // the offsets are not this call's plan: nothing was written outside them
 }

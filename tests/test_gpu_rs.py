@@ -89,6 +89,62 @@ def test_consensus_and_list_chain():
     assert rs_code.consensus([(3, b"a"), (3, b"b"), (3, b"b"), (3, b"a"), (1, b"c")]) == R.consensus([(3, b"a"), (3, b"b"), (3, b"b"), (3, b"a"), (1, b"c")])
 
 
+def _encode_then_decode(L, data, redundancy, erased, ok=True, erasures=True):
+    """lva_rs_encode of data [cw][n_data], then lva_rs_decode of the codewords with position `erased` overwritten by the pad
+    symbol (listed as an erasure unless erasures is False) -> encoded, decoded, ok (None where ok is False: NULL is passed)"""
+    cw, nd = data.shape
+    enc = np.zeros((cw, nd + redundancy), np.uint16)
+    assert L.lva_rs_encode(0, data.ctypes.data, cw, nd, redundancy, rs_code.PAD, enc.ctypes.data) == 0, L.lva_rs_last_error()
+    rx = enc.copy()
+    rx[:, erased] = rs_code.PAD
+    er = np.array([erased], np.int32)
+    dec = np.full((cw, nd), 0xFFFF, np.uint16)
+    okv = np.full(cw, -1, np.int32) if ok else None
+    st = L.lva_rs_decode(0, rx.ctypes.data, cw, nd + redundancy, redundancy, er.ctypes.data if erasures else None,
+                         1 if erasures else 0, rs_code.PAD, rs_code.PAD, dec.ctypes.data, okv.ctypes.data if ok else None)
+    assert st == 0, (st, L.lva_rs_last_error())
+    return enc, dec, okv
+
+
+def test_rs_beside_an_open_stream():
+    """The RS calls work on a stream of their own: beside a decode stream with reads in flight on the same device neither
+    side disturbs the other -- same RS outputs as with no stream open, same lists as a plain decode."""
+    import nanopore_dna_storage_amd as pkg
+    from nanopore_dna_storage_amd import synth
+    from nanopore_dna_storage_amd._lib import load_library
+    L = load_library()
+    data = np.random.default_rng(41).integers(0, 1 << 16, size=(2, 6)).astype(np.uint16)      # 2 codewords, n_total = 8
+    alone = _encode_then_decode(L, data, 2, 3)
+    assert np.array_equal(alone[1], data) and alone[2].tolist() == [1, 1] and np.array_equal(alone[0][:, :6], data)
+    reads = synth.make_reads(6, 1, 30, 2, seed0=77, margin=5.0)
+    with pkg.Decoder(6, 1, 30, list_size=2, max_deviation=20, device=0, max_slots=4) as dec:
+        want = dec.decode([x["post"] for x in reads])
+        with dec.stream() as st:
+            for i, x in enumerate(reads):
+                assert st.submit(x["post"], tag=i)
+            beside = _encode_then_decode(L, data, 2, 3)
+            got = {}
+            while len(got) < 2:
+                got.update(st.poll(wait=True))
+    for a, b in zip(alone, beside):
+        assert np.array_equal(a, b)
+    for i in range(2):
+        assert not isinstance(got[i], int) and not isinstance(want[i], int)
+        assert np.array_equal(got[i][0], want[i][0]) and np.array_equal(got[i][1], want[i][1])
+
+
+def test_rs_decode_optional_outputs():
+    """ok = NULL (an output nobody takes) and n_erasures = 0 (a piece of count 0): the same `out` as with ok given"""
+    from nanopore_dna_storage_amd._lib import load_library
+    L = load_library()
+    data = np.random.default_rng(42).integers(0, 1 << 16, size=(2, 6)).astype(np.uint16)
+    for erasures in (True, False):             # without the list the overwritten symbol is one error: redundancy 2 corrects it
+        enc, dec, ok = _encode_then_decode(L, data, 2, 3, ok=True, erasures=erasures)
+        assert np.array_equal(dec, data) and ok.tolist() == [1, 1]
+        enc2, dec2, none = _encode_then_decode(L, data, 2, 3, ok=False, erasures=erasures)
+        assert none is None and np.array_equal(enc2, enc) and np.array_equal(dec2, dec)
+
+
 def test_argument_errors():
     import ctypes
     from nanopore_dna_storage_amd._lib import load_library
