@@ -108,8 +108,8 @@ typedef struct lva_profile {
 const char *lva_version(void);
 /* LVA_ABI_VERSION of the library that was loaded.  It changes whenever a struct of this header changes size or layout
  * (5: lva_profile gained overflow_steps and working_bytes): a caller built against another value must not pass structs.
- * Entry points added since (lva_stream_*, lva_transpost_*, lva_device_download, lva_list_*, lva_demux_*, lva_kernel_plan)
- * change no struct and keep it at 5. */
+ * Entry points added since (lva_stream_*, lva_transpost_*, lva_device_download, lva_list_*, lva_demux_*, lva_kernel_plan,
+ * lva_align_profile) change no struct and keep it at 5. */
 #define LVA_ABI_VERSION 5
 int lva_abi_version(void);
 const char *lva_strerror(int code);
@@ -561,6 +561,37 @@ int lva_simulate_pool_fill_device(lva_decoder *d, uint64_t seed, uint32_t first_
                                   float margin, float clip, const int64_t *row_offsets, const int64_t *base_offsets,
                                   float *scores_dev, uint8_t *msgs_out, uint8_t *bases_out, uint8_t *true_idx_out,
                                   int32_t *source_out, uint8_t *rc_out);
+
+/* ---------------------------------------------------------------------------------------------
+ * the error profile of a set of reads -- every read aligned to the oligo it names, its matches,
+ * substitutions, deletions and insertions tallied by oligo position.
+ * replaces: util/align_compute_stats.sh:45-52 (minimap2 + samtools stats) and util/compile_plot_stats.py (the counts ->
+ * <prefix>.error_stats.csv); the mapping step is the index that lva_list_filter accepted, or a simulator's truth.
+ * The definition is nanopore_dna_storage_amd/error_profile.py (reference_profile):
+ *   a byte is a base if it is A C G T or 0 1 2 3, anything else is N and equals nothing, itself included;
+ *   read i is the window bases[first_base[i] .. first_base[i] + n_bases[i]) of one host buffer (windows may overlap),
+ *   reverse-complemented first when rc[i] != 0 (N stays N), and is aligned to refs[ref_id[i]] (refs [n_refs][ref_len]);
+ *   D is the unit-cost global edit-distance matrix, D[i][0] = i, D[0][j] = j, i over reference positions, j over the window;
+ *   the walk starts at (ref_len, n) and takes at (i, j) the first move that applies: diagonal if i, j > 0 and
+ *   D[i-1][j-1] + (ref[i-1] != read[j-1]) == D[i][j] (a match or a substitution at position i-1), up if i > 0 and
+ *   D[i-1][j] + 1 == D[i][j] (a deletion at position i-1), else left (an insertion in front of position i).
+ * Outputs, each may be NULL:
+ *   out_read [n_reads][4]     (distance, substitutions, deletions, insertions); a read with ref_id[i] < 0 is skipped: its row
+ *                             is four times -1 and it adds nothing below;
+ *   out_pos  [ref_len + 1][4] per oligo position (matches, substitutions, deletions, bases inserted in front of it); the first
+ *                             three are 0 in row ref_len;
+ *   out_conf [4][6]           per reference base A C G T how often it was read as A, C, G, T, N or deleted (a reference N counts
+ *                             in no row here, but does in out_pos);
+ *   out_ins  [5]              inserted bases by value A C G T N.
+ * 1 <= ref_len <= 1024, 0 <= n_bases[i] <= 4096, n_refs >= 1, n_refs * ref_len < 2^31, ref_id[i] < n_refs, first_base[i] >= 0,
+ * the sum of n_bases below 2^31; chunk_reads reads at a time on the device (0, or more than fit: as many as fit 1 GiB); the
+ * result does not depend on it.  All results are exact integers.  Takes a device ordinal like the lva_list_* calls and
+ * behaves like them: arguments first (LVA_ERR_ARG), then n_reads = 0 succeeds and touches nothing, then the device.
+ * ------------------------------------------------------------------------------------------- */
+int lva_align_profile(int32_t device, const uint8_t *bases, const int64_t *first_base, const int32_t *n_bases, int32_t n_reads,
+                      const uint8_t *refs, int32_t n_refs, int32_t ref_len, const int32_t *ref_id,
+                      const uint8_t *rc /* NULL: none */, int32_t chunk_reads /* 0: as many as fit 1 GiB */, int32_t *out_read,
+                      int64_t *out_pos, int64_t *out_conf, int64_t *out_ins);
 
 #ifdef __cplusplus
 }

@@ -144,6 +144,7 @@ ABI = {
     "lva_simulate_fill_device": (_int, _sim + [_f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lva_simulate_pool_plan": (_int, _sim + _pool + [_vp, _vp]),
     "lva_simulate_pool_fill_device": (_int, _sim + _pool + [_f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lva_align_profile": (_int, [_i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
 }
 EXPORTS = list(ABI)
 

@@ -1,6 +1,6 @@
 // lva_stages.cpp -- C ABI (include/lva_decoder.h) of the stages beside the list decoder: transition posteriors (N0), basecall
 // and barcode localisation (N3), demultiplexing (N3'), the consumers of a decoded list (N2), the Reed-Solomon outer code (N4),
-// reading-cost trials (N4'), the read simulator (S).  No algorithm lives here: an entry point checks its arguments, then works
+// reading-cost trials (N4'), the read simulator (S), the error profile (N5).  No algorithm lives here: an entry point checks its arguments, then works
 // through one Frame (below): it declares its device pieces together with their host side, begins (allocate, upload),
 // launches, finishes (copy back, wait).
 #include <algorithm>
@@ -13,6 +13,7 @@
 #include "rs_kernels.h"
 #include "sim_kernels.h"
 #include "tr_kernels.h"
+#include "ep_kernels.h"
 
 using namespace lva;
 
@@ -929,6 +930,93 @@ int lva_simulate_pool_fill_device(lva_decoder* d, uint64_t seed, uint32_t first_
   return simulate_fill(d, seed, first_read, n_reads, sub_thr, del_thr, ins_thr, dwell_cdf, dwell_k, start_barcode, end_barcode,
                        flank_lo, flank_hi, rc_mode, &ph, scale, margin, clip, row_offsets, base_offsets, scores_dev, msgs_out,
                        bases_out, true_idx_out, source_out, rc_out);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// the error profile of a set of reads (csrc/ep_kernels.hip; the definition is
+// error_profile.py).  Like the list consumers: a device ordinal, a stream of its own, complete on return.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+constexpr size_t kEpChunkBytes = (size_t)1 << 30;        // what the move codes of a chunk of reads may occupy on the device
+
+// everything lva_align_profile can refuse without the device; *total = bases of the reads that are not skipped
+int profile_args(const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases, int32_t n_reads, const uint8_t* refs,
+                 int32_t n_refs, int32_t ref_len, const int32_t* ref_id, int32_t chunk_reads, size_t* total) {
+  if (n_reads < 0 || chunk_reads < 0 || !refs) return LVA_ERR_ARG;
+  if (ref_len < 1 || ref_len > kEpMaxRef || n_refs < 1 || (uint64_t)n_refs * (uint64_t)ref_len >= (1ull << 31)) return LVA_ERR_ARG;
+  if (n_reads > 0 && (!bases || !first_base || !n_bases || !ref_id)) return LVA_ERR_ARG;
+  uint64_t sum = 0, kept = 0;
+  for (int32_t i = 0; i < n_reads; ++i) {
+    if (first_base[i] < 0 || n_bases[i] < 0 || n_bases[i] > kEpMaxRead || ref_id[i] >= n_refs) return LVA_ERR_ARG;
+    sum += (uint64_t)n_bases[i];
+    if (ref_id[i] >= 0) kept += (uint64_t)n_bases[i];
+  }
+  if (sum >= (1ull << 31)) return LVA_ERR_ARG;
+  *total = (size_t)kept;
+  return LVA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lva_align_profile(int32_t device, const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases, int32_t n_reads,
+                      const uint8_t* refs, int32_t n_refs, int32_t ref_len, const int32_t* ref_id, const uint8_t* rc,
+                      int32_t chunk_reads, int32_t* out_read, int64_t* out_pos, int64_t* out_conf, int64_t* out_ins) {
+  size_t total = 0;
+  if (profile_args(bases, first_base, n_bases, n_reads, refs, n_refs, ref_len, ref_id, chunk_reads, &total) != LVA_OK) return LVA_ERR_ARG;
+  if (n_reads == 0) return LVA_OK;
+  const size_t n = (size_t)n_reads, np = 4 * ((size_t)ref_len + 1);
+  std::vector<uint8_t> packed, flip;                     // (these outlive the call's frame)
+  std::vector<int32_t> win_off, nb;
+  std::vector<int64_t> move_off, zero;
+  Frame f;
+  if (const int so = f.open(device)) return so;
+  // the windows of the reads that are not skipped, one after the other (windows may overlap, or lie far apart, in `bases`)
+  packed.resize(total); flip.assign(n, 0);
+  win_off.resize(n); nb.resize(n); move_off.resize(n);
+  zero.assign(std::max<size_t>(np, 24), 0);
+  // chunks: reads [cuts[k], cuts[k + 1]), as many as chunk_reads allows and as fit kEpChunkBytes (one read: at most 4.3 MB)
+  std::vector<size_t> cuts{0};
+  size_t at = 0, in_chunk = 0, cap = 0;
+  for (size_t i = 0; i < n; ++i) {
+    nb[i] = ref_id[i] < 0 ? 0 : n_bases[i];
+    win_off[i] = (int32_t)at;
+    if (nb[i] > 0) std::memcpy(packed.data() + at, bases + first_base[i], (size_t)nb[i]);
+    at += (size_t)nb[i];
+    if (rc && rc[i]) flip[i] = 1;
+    const size_t mb = ep_move_bytes(ref_len, nb[i]);
+    if (i > cuts.back() && (in_chunk + mb > kEpChunkBytes || (chunk_reads > 0 && i - cuts.back() >= (size_t)chunk_reads))) {
+      cuts.push_back(i);
+      in_chunk = 0;
+    }
+    move_off[i] = (int64_t)in_chunk;                     // from the start of the chunk's moves
+    in_chunk += mb;
+    cap = std::max(cap, in_chunk);
+  }
+  cuts.push_back(n);
+  const auto d_bases = f.in(packed.data(), total);
+  const auto d_win = f.in(win_off.data(), n), d_nb = f.in(nb.data(), n), d_id = f.in(ref_id, n);
+  const auto d_flip = f.in(flip.data(), n);
+  const auto d_moff = f.in(move_off.data(), n);
+  const auto d_refs = f.in(refs, (size_t)n_refs * (size_t)ref_len);
+  const auto d_moves = f.scratch<uint8_t>(cap);
+  const auto d_read = f.out(out_read, 4 * n);
+  const auto d_pos = f.inout(zero.data(), out_pos, np), d_conf = f.inout(zero.data(), out_conf, 24), d_ins = f.inout(zero.data(), out_ins, 5);
+  if (const int st = f.begin()) return st;
+  for (size_t k = 0; k + 1 < cuts.size(); ++k) {         // the tallies are sums over reads: chunks change nothing
+    const size_t a = cuts[k];
+    const int32_t c = (int32_t)(cuts[k + 1] - a);
+    int e = launch_ep_fill(d_bases, d_win.ptr() + a, d_nb.ptr() + a, c, d_refs, ref_len, d_id.ptr() + a, d_flip.ptr() + a,
+                           d_moff.ptr() + a, d_moves, f.stream());
+    if (!e) e = launch_ep_walk(d_bases, d_win.ptr() + a, d_nb.ptr() + a, c, d_refs, ref_len, d_id.ptr() + a, d_flip.ptr() + a,
+                               d_moff.ptr() + a, d_moves, d_read.ptr() + 4 * a, d_pos, d_conf, d_ins, f.stream());
+    if (e) return launch_status(e);
+  }
+  return f.finish();
 }
 
 }  // extern "C"

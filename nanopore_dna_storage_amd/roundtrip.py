@@ -7,7 +7,9 @@
             (trials.run_trials) over the filtered reads, printed as that tool prints them.
 
 Reads are made and decoded --chunk at a time, so that the scores in HBM stay bounded; read number k depends on (--seed, k)
-alone, so nothing that is written or printed depends on --chunk.  --coverage_weights FILE: one non-negative weight per oligo
+alone, so nothing that is written or printed depends on --chunk.  --error_profile PREFIX: the reads as the channel emitted
+them are aligned to the oligos they were drawn from (error_profile.align_profile; the reference of a read is the truth's
+source, its orientation the truth's rc) and PREFIX.error_stats.csv is written: what the channel did, measured.  --coverage_weights FILE: one non-negative weight per oligo
 (whitespace-separated, in the oligo file's order), uneven coverage; without it every oligo is as likely as any other.  Every
 read's orientation is a coin (rc_mode 3) and is handed to the decoder as drawn."""
 import argparse
@@ -19,9 +21,9 @@ import tempfile
 
 import numpy as np
 
-from . import helper, list_ops, rs_code, simulate
+from . import error_profile, helper, list_ops, rs_code, simulate
 from .decode_RS_from_decoded_lists import print_curve, sample_sizes
-from .decoder import Decoder
+from .decoder import Decoder, encode
 
 
 def build_parser():
@@ -45,24 +47,32 @@ def build_parser():
     p.add_argument("--num_trials", type=int, default=10)
     p.add_argument("--out", type=str, default=None, help="the recovered file (default: DATA_FILE.recovered), or the file the curve is written to")
     p.add_argument("--device", type=int, default=0)
+    p.add_argument("--error_profile", type=str, default=None, metavar="PREFIX",
+                   help="also align the simulated reads to their oligos and write PREFIX.error_stats.csv")
     return p
 
 
-def filtered_reads(a, pool, pool_cdf, num_oligos, decoder=None):
+def filtered_reads(a, pool, pool_cdf, num_oligos, decoder=None, profiles=None):
     """reads 0 .. num_reads - 1 of the pool, made, decoded and filtered --chunk at a time
-    -> (index int32 [num_reads] with -1 where no entry passed, payload uint8 [num_reads, bytes_per_oligo])"""
+    -> (index int32 [num_reads] with -1 where no entry passed, payload uint8 [num_reads, bytes_per_oligo]);
+    profiles: a list that receives every chunk's ErrorProfile against the truth (--error_profile)"""
     msg_len = pool.shape[1]
+    oligos = encode(a.mem_conv, a.rate_conv, msg_len, pool) if profiles is not None else None
     own = decoder is None
     dec = Decoder(a.mem_conv, a.rate_conv, msg_len, list_size=a.list_size, max_deviation=20, device=a.device) if own else decoder
     index, payload = [np.zeros(0, np.int32)], [np.zeros((0, a.bytes_per_oligo), np.uint8)]
     try:
         for first in range(0, a.num_reads, a.chunk):
-            _, results = dec.simulate_and_decode(min(a.chunk, a.num_reads - first), a.seed, first_read=first, pool=pool,
+            truth, results = dec.simulate_and_decode(min(a.chunk, a.num_reads - first), a.seed, first_read=first, pool=pool,
                                                  pool_cdf=pool_cdf, rc_mode=3, sub=a.sub, dele=a.dele, ins=a.ins, margin=a.margin)
             msgs, counts = list_ops.results_to_array(results, dec.list_size, msg_len)
             k, _, p = list_ops.filter_lists(msgs, counts, a.bytes_per_oligo, num_oligos, device=a.device)
             index.append(k)
             payload.append(p)
+            if profiles is not None:
+                base = truth["base_offsets"]
+                profiles.append(error_profile.align_profile(truth["bases"], np.stack([base[:-1], np.diff(base)], axis=1), oligos,
+                                                            truth["source"], rc=truth["rc"], device=a.device))
     finally:
         if own:
             dec.close()
@@ -90,8 +100,15 @@ def main(argv=None, out=sys.stdout, decoder=None):
         if len(weights) != len(pool):
             parser.error("--coverage_weights: %d weights for %d oligos" % (len(weights), len(pool)))
         pool_cdf = simulate.weights_to_cdf(weights)
-    index, payload = filtered_reads(a, pool, pool_cdf, num_oligos, decoder)
+    profiles = [] if a.error_profile is not None else None
+    index, payload = filtered_reads(a, pool, pool_cdf, num_oligos, decoder, profiles)
     res = dict(index=index, payload=payload)
+    if profiles is not None:
+        profile = profiles[0]
+        for part in profiles[1:]:
+            profile = profile + part
+        profile.write_csv(a.error_profile)
+        res.update(error_profile=profile)
     if a.num_reads_to_use is not None:
         from . import trials
         stats = trials.run_trials(index, payload, original, a.bytes_per_oligo, num_oligos_RS, num_oligos, a.num_reads_to_use,
