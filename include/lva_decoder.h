@@ -109,7 +109,7 @@ const char *lva_version(void);
 /* LVA_ABI_VERSION of the library that was loaded.  It changes whenever a struct of this header changes size or layout
  * (5: lva_profile gained overflow_steps and working_bytes): a caller built against another value must not pass structs.
  * Entry points added since (lva_stream_*, lva_transpost_*, lva_device_download, lva_list_*, lva_demux_*, lva_kernel_plan,
- * lva_align_profile) change no struct and keep it at 5. */
+ * lva_align_profile, lva_map_index_*, lva_map_reads) change no struct and keep it at 5. */
 #define LVA_ABI_VERSION 5
 int lva_abi_version(void);
 const char *lva_strerror(int code);
@@ -592,6 +592,36 @@ int lva_align_profile(int32_t device, const uint8_t *bases, const int64_t *first
                       const uint8_t *refs, int32_t n_refs, int32_t ref_len, const int32_t *ref_id,
                       const uint8_t *rc /* NULL: none */, int32_t chunk_reads /* 0: as many as fit 1 GiB */, int32_t *out_read,
                       int64_t *out_pos, int64_t *out_conf, int64_t *out_ins);
+
+/* ---------------------------------------------------------------------------------------------
+ * reads mapped to oligos -- for reads that carry no index of their own (a list that failed the
+ * CRC, barcodes that were not found), and for coverage per oligo from real reads.
+ * replaces: util/align_compute_stats.sh:21-33 (minimap2 against merged.fa); no agreement with minimap2 is claimed.
+ * The definition is nanopore_dna_storage_amd/read_map.py (reference_map); bytes are read as lva_align_profile reads them:
+ *   index    the distinct pairs (k-mer, oligo) over every oligo position whose k bases are all bases, 2 bits per base, first
+ *            base most significant; a k-mer held by more than max_occ oligos is dropped; ref_len < k: an empty index;
+ *   votes    per strand (0: the window, 1: its reverse complement) and oligo, the window positions whose k-mer the oligo holds;
+ *   cands    the (strand, oligo) pairs with at least min_votes votes, by (votes descending, strand, oligo): the first `cands`;
+ *   dist     D[i][0] = i, D[0][j] = 0, unit costs, oligo rows against window columns: d = min_j D[m][j], e the first such j;
+ *   winner   the smallest (d, place among the candidates); second: the smallest d of a candidate with another oligo, or -1;
+ *   start    the reversed oligo against window[0:e] reversed, E[i][0] = i, E[0][j] = j: j' the first j with E[m][j] = d.
+ * out [n_reads][8] = (ref, best, rc, dist, start, count, votes, second): best the winner's oligo, ref = best if dist <=
+ * max_dist, else -1; [start, start + count) the aligned part in the coordinates of the window as given; a read without a
+ * candidate: (-1, -1, 0, -1, 0, 0, 0, -1).  The global distance of that part to the oligo is dist, so (start, count, ref,
+ * rc) are arguments of lva_align_profile.
+ * lva_map_index_create is host-only: 1 <= ref_len <= 1024, 6 <= k <= 12, 1 <= max_occ <= 65535, n_refs >= 1, n_refs *
+ * ref_len < 2^31.  lva_map_reads: 1 <= cands <= 8, min_votes >= 1, max_dist >= 0, 0 <= n_bases[i] <= 4096, first_base[i] >=
+ * 0, the sum of n_bases below 2^31; chunk_reads reads at a time on the device (0: as many as fit 1 GiB of candidate lists),
+ * the result does not depend on it.  Arguments first (LVA_ERR_ARG), then n_reads = 0 succeeds, then the device.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct lva_map_index lva_map_index;
+int lva_map_index_create(const uint8_t *refs, int32_t n_refs, int32_t ref_len, int32_t k, int32_t max_occ, lva_map_index **out);
+void lva_map_index_destroy(lva_map_index *idx);
+/* kept distinct k-mers, kept pairs, k-mers dropped by max_occ; each output may be NULL */
+int lva_map_index_info(const lva_map_index *idx, int64_t *kmers, int64_t *pairs, int64_t *dropped_kmers);
+int lva_map_reads(int32_t device, const lva_map_index *idx, const uint8_t *bases, const int64_t *first_base, const int32_t *n_bases,
+                  int32_t n_reads, int32_t cands, int32_t min_votes, int32_t max_dist,
+                  int32_t chunk_reads /* 0: as many as fit */, int32_t *out);
 
 #ifdef __cplusplus
 }

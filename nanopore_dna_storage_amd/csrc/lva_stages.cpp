@@ -1,10 +1,11 @@
 // lva_stages.cpp -- C ABI (include/lva_decoder.h) of the stages beside the list decoder: transition posteriors (N0), basecall
 // and barcode localisation (N3), demultiplexing (N3'), the consumers of a decoded list (N2), the Reed-Solomon outer code (N4),
-// reading-cost trials (N4'), the read simulator (S), the error profile (N5).  No algorithm lives here: an entry point checks its arguments, then works
+// reading-cost trials (N4'), the read simulator (S), the error profile (N5), read mapping (N6).  No algorithm lives here: an entry point checks its arguments, then works
 // through one Frame (below): it declares its device pieces together with their host side, begins (allocate, upload),
 // launches, finishes (copy back, wait).
 #include <algorithm>
 #include <cstring>
+#include <new>
 
 #include "lva_host.h"
 #include "bc_kernels.h"
@@ -14,6 +15,7 @@
 #include "sim_kernels.h"
 #include "tr_kernels.h"
 #include "ep_kernels.h"
+#include "mp_kernels.h"
 
 using namespace lva;
 
@@ -1014,6 +1016,162 @@ int lva_align_profile(int32_t device, const uint8_t* bases, const int64_t* first
                            d_moff.ptr() + a, d_moves, f.stream());
     if (!e) e = launch_ep_walk(d_bases, d_win.ptr() + a, d_nb.ptr() + a, c, d_refs, ref_len, d_id.ptr() + a, d_flip.ptr() + a,
                                d_moff.ptr() + a, d_moves, d_read.ptr() + 4 * a, d_pos, d_conf, d_ins, f.stream());
+    if (e) return launch_status(e);
+  }
+  return f.finish();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// reads mapped to oligos (csrc/mp_kernels.hip; the definition is read_map.py).  The index is
+// built on the host once and owned by the caller; a mapping call takes a device ordinal like the list consumers.
+// ---------------------------------------------------------------------------------------------
+struct lva_map_index {
+  int32_t n_refs, ref_len, k, max_occ;
+  std::vector<uint32_t> offsets;         // [4^k + 1]: the oligos of k-mer c are lists[offsets[c] .. offsets[c + 1])
+  std::vector<int32_t> lists;            // ascending inside a k-mer
+  std::vector<uint64_t> masks;           // mp_mask_words: per oligo, forward and reversed, per base, W words
+  int64_t kmers, pairs, dropped;         // kept distinct k-mers, kept pairs, k-mers that max_occ dropped
+};
+
+namespace {
+
+constexpr size_t kMpChunkBytes = (size_t)1 << 30;        // what the candidate lists of a chunk of reads may occupy on the device
+
+inline uint32_t mp_base(uint8_t b) {                     // as the kernels read a byte
+  switch (b) {
+    case 'A': case 0: return 0;
+    case 'C': case 1: return 1;
+    case 'G': case 2: return 2;
+    case 'T': case 3: return 3;
+    default: return 4;
+  }
+}
+
+// everything lva_map_reads can refuse without the device; *total = bases of all windows
+int map_args(const lva_map_index* idx, const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases, int32_t n_reads,
+             int32_t cands, int32_t min_votes, int32_t max_dist, int32_t chunk_reads, const int32_t* out, size_t* total) {
+  if (!idx || n_reads < 0 || chunk_reads < 0 || cands < 1 || cands > kMpMaxCands || min_votes < 1 || max_dist < 0) return LVA_ERR_ARG;
+  if (n_reads > 0 && (!bases || !first_base || !n_bases || !out)) return LVA_ERR_ARG;
+  uint64_t sum = 0;
+  for (int32_t i = 0; i < n_reads; ++i) {
+    if (first_base[i] < 0 || n_bases[i] < 0 || n_bases[i] > kMpMaxRead) return LVA_ERR_ARG;
+    sum += (uint64_t)n_bases[i];
+  }
+  if (sum >= (1ull << 31)) return LVA_ERR_ARG;
+  *total = (size_t)sum;
+  return LVA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lva_map_index_create(const uint8_t* refs, int32_t n_refs, int32_t ref_len, int32_t k, int32_t max_occ, lva_map_index** out) {
+  static_assert(kMpMaxRef == kEpMaxRef && kMpMaxRead == kEpMaxRead, "a mapped window is one lva_align_profile accepts");
+  if (!refs || !out || n_refs < 1 || ref_len < 1 || ref_len > kMpMaxRef || k < kMpMinK || k > kMpMaxK) return LVA_ERR_ARG;
+  if (max_occ < 1 || max_occ > 65535 || (uint64_t)n_refs * (uint64_t)ref_len >= (1ull << 31)) return LVA_ERR_ARG;
+  lva_map_index* x = new (std::nothrow) lva_map_index{};
+  if (!x) return LVA_ERR_NOMEM;
+  try {
+    x->n_refs = n_refs; x->ref_len = ref_len; x->k = k; x->max_occ = max_occ;
+    const size_t m = (size_t)ref_len, W = (m + 63) / 64, table = (size_t)1 << (2 * k);
+    // the distinct pairs (k-mer, oligo), k-mer major
+    std::vector<uint64_t> pairs;
+    const uint32_t mask = (uint32_t)(table - 1);
+    x->masks.assign(mp_mask_words(n_refs, ref_len), 0);
+    for (int32_t o = 0; o < n_refs; ++o) {
+      const uint8_t* ref = refs + (size_t)o * m;
+      uint32_t code = 0;
+      int run = 0;
+      for (size_t i = 0; i < m; ++i) {
+        const uint32_t c = mp_base(ref[i]);
+        if (c < 4) {
+          code = ((code << 2) | c) & mask;
+          ++run;
+          x->masks[(((size_t)o * 2 + 0) * 4 + c) * W + (i >> 6)] |= 1ull << (i & 63);
+          x->masks[(((size_t)o * 2 + 1) * 4 + c) * W + ((m - 1 - i) >> 6)] |= 1ull << ((m - 1 - i) & 63);
+        } else {
+          run = 0;
+        }
+        if (run >= k) pairs.push_back(((uint64_t)code << 32) | (uint32_t)o);
+      }
+    }
+    std::sort(pairs.begin(), pairs.end());
+    pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+    x->offsets.assign(table + 1, 0);
+    x->lists.reserve(pairs.size());
+    size_t at = 0;
+    for (size_t c = 0; c < table; ++c) {
+      x->offsets[c] = (uint32_t)x->lists.size();
+      size_t end = at;
+      while (end < pairs.size() && (pairs[end] >> 32) == c) ++end;
+      if (end > at) {
+        if (end - at > (size_t)max_occ) {
+          ++x->dropped;                  // shared too widely to say anything: it votes for nobody
+        } else {
+          ++x->kmers;
+          for (size_t p = at; p < end; ++p) x->lists.push_back((int32_t)(pairs[p] & 0xFFFFFFFFu));
+        }
+      }
+      at = end;
+    }
+    x->offsets[table] = (uint32_t)x->lists.size();
+    x->pairs = (int64_t)x->lists.size();
+  } catch (const std::bad_alloc&) {
+    delete x;
+    return LVA_ERR_NOMEM;
+  }
+  *out = x;
+  return LVA_OK;
+}
+
+void lva_map_index_destroy(lva_map_index* idx) { delete idx; }
+
+int lva_map_index_info(const lva_map_index* idx, int64_t* kmers, int64_t* pairs, int64_t* dropped_kmers) {
+  if (!idx) return LVA_ERR_ARG;
+  if (kmers) *kmers = idx->kmers;
+  if (pairs) *pairs = idx->pairs;
+  if (dropped_kmers) *dropped_kmers = idx->dropped;
+  return LVA_OK;
+}
+
+int lva_map_reads(int32_t device, const lva_map_index* idx, const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases,
+                  int32_t n_reads, int32_t cands, int32_t min_votes, int32_t max_dist, int32_t chunk_reads, int32_t* out) {
+  size_t total = 0;
+  if (map_args(idx, bases, first_base, n_bases, n_reads, cands, min_votes, max_dist, chunk_reads, out, &total) != LVA_OK) return LVA_ERR_ARG;
+  if (n_reads == 0) return LVA_OK;
+  const size_t n = (size_t)n_reads;
+  std::vector<uint8_t> packed;                           // (these outlive the call's frame)
+  std::vector<int32_t> win_off;
+  Frame f;
+  if (const int so = f.open(device)) return so;
+  // the windows one after the other (windows may overlap, or lie far apart, in `bases`)
+  packed.resize(total); win_off.resize(n);
+  size_t at = 0;
+  for (size_t i = 0; i < n; ++i) {
+    win_off[i] = (int32_t)at;
+    if (n_bases[i] > 0) std::memcpy(packed.data() + at, bases + first_base[i], (size_t)n_bases[i]);
+    at += (size_t)n_bases[i];
+  }
+  size_t chunk = std::min(n, kMpChunkBytes / (kMpMaxCands * sizeof(uint64_t)));
+  if (chunk_reads > 0) chunk = std::min(chunk, (size_t)chunk_reads);
+  const auto d_bases = f.in(packed.data(), total);
+  const auto d_win = f.in(win_off.data(), n), d_nb = f.in(n_bases, n);
+  const auto d_off = f.in(idx->offsets.data(), idx->offsets.size());
+  const auto d_lists = f.in(idx->lists.data(), idx->lists.size());
+  const auto d_masks = f.in(idx->masks.data(), idx->masks.size());
+  const auto d_cand = f.scratch<uint64_t>(chunk * kMpMaxCands);
+  const auto d_out = f.out(out, 8 * n);
+  if (const int st = f.begin()) return st;
+  for (size_t a = 0; a < n; a += chunk) {                // a read's row depends on the read alone: chunks change nothing
+    const int32_t c = (int32_t)std::min(chunk, n - a);
+    int e = launch_mp_vote(d_bases, d_win.ptr() + a, d_nb.ptr() + a, c, d_off, d_lists, idx->k, idx->n_refs, min_votes, cands, d_cand,
+                           f.stream());
+    if (!e) e = launch_mp_verify(d_bases, d_win.ptr() + a, d_nb.ptr() + a, c, d_cand, d_masks, idx->ref_len, cands, max_dist,
+                                 d_out.ptr() + 8 * a, f.stream());
+    if (!e) e = launch_mp_start(d_bases, d_win.ptr() + a, d_nb.ptr() + a, c, d_masks, idx->ref_len, d_out.ptr() + 8 * a, f.stream());
     if (e) return launch_status(e);
   }
   return f.finish();

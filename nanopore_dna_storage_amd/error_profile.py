@@ -228,6 +228,19 @@ def profile_decoded(dec, dev, off, located_results, filter_index, oligos, device
                          device=dec.device if device is None else device)
 
 
+def profile_mapped(dec, dev, off, index, cands=4, min_votes=2, max_dist=None, device=None):
+    """The profile of reads that name no oligo: one basecall_resident call over a resident posterior buffer (dev, off), the
+    whole basecalls mapped to the oligos of `index` (a read_map.MapIndex; read_map.map_reads), and the mapped parts aligned to
+    the oligo and on the strand the mapping found.  No list is decoded and no barcode is looked for, so reads whose list
+    failed the CRC are counted.  -> (ErrorProfile, read_map.MapResult)"""
+    from . import read_map
+    device = dec.device if device is None else device
+    calls = [b for b, _ in dec.basecall_resident(dev, off)]
+    bases, win = "".join(calls), read_map.whole_windows(calls)
+    res = read_map.map_reads(bases, win, index, cands, min_votes, max_dist, device=device)
+    return align_profile(bases, res.windows(win), index.refs, res.ref, res.rc, device=device), res
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="error profile of basecalled reads against their oligos: locate, decode, filter, "
                                             "align, <out_prefix>.error_stats.csv")
@@ -243,11 +256,14 @@ def build_parser():
     p.add_argument("--max_deviation", type=int, default=20)
     p.add_argument("--chunk", type=int, default=4096, help="reads per pass over the manifest")
     p.add_argument("--device", type=int, default=0)
+    p.add_argument("--assign", choices=("filter", "map"), default="filter",
+                   help="a read's oligo: the index its decoded list passed the CRC with, or read_map's mapping of its whole basecall "
+                        "(no list is decoded)")
     return p
 
 
 def main(argv=None, out=sys.stdout, decoder=None):
-    """-> the ErrorProfile of the manifest's reads whose list passed the filter"""
+    """-> the ErrorProfile of the manifest's reads whose list passed the filter (--assign map: that were mapped)"""
     from . import helper, list_ops
     from .decoder import Decoder
     a = build_parser().parse_args(argv)
@@ -260,24 +276,34 @@ def main(argv=None, out=sys.stdout, decoder=None):
         raise SystemExit("--msg_len is not 12 + 8 * bytes_per_oligo + 8 (+ 1), or the oligo file is empty")
     own = decoder is None
     dec = Decoder(a.mem_conv, a.rate_conv, a.msg_len, list_size=a.list_size, max_deviation=a.max_deviation, device=a.device) if own else decoder
-    total = None
+    total, mapped, map_index = None, 0, None
     try:
+        if a.assign == "map":
+            from .read_map import MapIndex
+            map_index = MapIndex(oligos)
         for k in range(0, len(paths), max(1, a.chunk)):
             with dec.resident([helper.read_post_file(p) for p in paths[k:k + max(1, a.chunk)]]) as (dev, off):
-                chain = dec.decode_located(dev, off, dec.locate_payload_resident(dev, off, a.start_barcode, a.end_barcode))
-                msgs, counts = list_ops.results_to_array([-100 if res is None else res for _, res in chain], dec.list_size, a.msg_len)
-                index, _, _ = list_ops.filter_lists(msgs, counts, bytes_per_oligo, len(oligos), pad=bool(pad), device=a.device)
-                part = profile_decoded(dec, dev, off, chain, index, oligos, device=a.device)
+                if map_index is not None:
+                    part, res = profile_mapped(dec, dev, off, map_index, device=a.device)
+                    mapped += res.mapped
+                else:
+                    chain = dec.decode_located(dev, off, dec.locate_payload_resident(dev, off, a.start_barcode, a.end_barcode))
+                    msgs, counts = list_ops.results_to_array([-100 if res is None else res for _, res in chain], dec.list_size, a.msg_len)
+                    index, _, _ = list_ops.filter_lists(msgs, counts, bytes_per_oligo, len(oligos), pad=bool(pad), device=a.device)
+                    part = profile_decoded(dec, dev, off, chain, index, oligos, device=a.device)
             total = part if total is None else total + part
     finally:
+        if map_index is not None:
+            map_index.close()
         if own:
             dec.close()
+    counted = ["reads:", len(paths)] + (["mapped:", mapped] if a.assign == "map" else [])
     if total is None or total.reads == 0:
-        print("reads:", len(paths), "aligned: 0", file=out)
+        print(*counted, "aligned: 0", file=out)
         return total
     total.write_csv(a.out_prefix)
     r = total.rates()
-    print("reads:", len(paths), "aligned:", total.reads, file=out)
+    print(*counted, "aligned:", total.reads, file=out)
     print("sub %.6f dele %.6f ins %.6f per reference base" % (r["sub"], r["dele"], r["ins"]), file=out)
     return total
 
