@@ -4,10 +4,13 @@
  *
  * TEST INFRASTRUCTURE ONLY (same rules as lva_oracle.h).
  *
- * PARITY UNPINNED: flappie's decode path cannot be built in this image -- decode.c links against
- * flappie_matrix.c, which includes <cblas.h> (absent), and the reference holds no golden vectors
- * for it.  This file restates the published algorithm line by line and is checked on
- * hand-computable cases and properties only (tests/test_basecall_oracle.py).
+ * PINNED to the compiled, unmodified decode_crf_flipflop / change_positions of the reference
+ * (oracle/_ref/flappie_decode.out, oracle/Makefile's `flappieref`): state path, score bits, change
+ * positions and bases are equal bit for bit on the cases of tests/flappie_cases.py, recorded in
+ * tests/golden/flappie_ref.npz (tests/test_flappie_pin.py) -- reads of 1 to 3000 blocks, an
+ * all-tie read, -inf entries.  Qualities (qpath, phredf) are not restated: the project produces
+ * none.  This file restates the algorithm line by line; tests/test_basecall_oracle.py holds it to
+ * hand-computable cases and properties as well.
  *
  * Restated:
  *   decode_crf_flipflop   flappie/src/decode.c:119-204  (combine_stays = false, flappie.c:273)

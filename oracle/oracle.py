@@ -179,8 +179,53 @@ def ref_decode(mem_conv, rate, msg_len, post, list_size, max_deviation=None, rc=
 
 
 # ---------------------------------------------------------------------------------------------
+# flappie's own decode path (oracle/_ref/flappie_decode.out: the reference's decode.c behind the
+# driver oracle/flappie_ref/flappie_ref_main.c, built by oracle/Makefile's `flappieref`)
+# ---------------------------------------------------------------------------------------------
+FLAPPIE_BIN = os.path.join(_HERE, "_ref", "flappie_decode.out")
+
+
+def have_flappie_ref():
+    return os.path.exists(FLAPPIE_BIN) and os.access(FLAPPIE_BIN, os.X_OK)
+
+
+def _flappie_run(mode, matrix):
+    matrix = np.ascontiguousarray(matrix, dtype=np.float32).reshape(-1, 40)
+    with tempfile.TemporaryDirectory() as d:
+        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
+        matrix.tofile(fin)
+        r = subprocess.run([FLAPPIE_BIN, mode, fin, fout], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+        if r.returncode != 0:
+            raise RuntimeError("flappie_decode.out %s failed rc=%d: %s" % (mode, r.returncode, r.stderr.decode()[:200]))
+        with open(fout, "rb") as f:
+            return matrix.shape[0], f.read()
+
+
+def flappie_transpost(scores):
+    """transpost_crf_flipflop(trans, true) of the compiled flappie: float32[nblk][40] scores -> float32[nblk][40] log-posteriors"""
+    nblk, raw = _flappie_run("transpost", scores)
+    return np.frombuffer(raw, dtype=np.float32).reshape(nblk, 40).copy()
+
+
+def flappie_basecall(post):
+    """decode_crf_flipflop(post, false, ..) + change_positions + flappie.c:276-285 of the compiled flappie ->
+    (basecall str, change positions int64, state path int32[nblk+1], score float32): the tuple basecall() returns"""
+    nblk, raw = _flappie_run("basecall", post)
+    assert int(np.frombuffer(raw, np.int32, 1, 0)[0]) == nblk
+    path = np.frombuffer(raw, np.int32, nblk + 1, 4).copy()
+    at = 4 * (nblk + 2)
+    score = np.frombuffer(raw, np.float32, 1, at)[0]
+    nch = int(np.frombuffer(raw, np.int32, 1, at + 4)[0])
+    chpos = np.frombuffer(raw, np.int32, nch, at + 8).astype(np.int64)
+    bases = raw[at + 8 + 4 * nch:]
+    assert len(bases) == nch
+    return bases.decode("ascii"), chpos, path, score
+
+
+# ---------------------------------------------------------------------------------------------
 # SURVEY.md section 8(f) row N3: flappie basecall of the .post matrix + barcode localisation.
-# PARITY UNPINNED for the basecall (see oracle/basecall_oracle.c); the barcode search restates
+# The basecall (oracle/basecall_oracle.c) is pinned to the compiled flappie above on the fixtures of
+# tests/golden/flappie_ref.npz (tests/test_flappie_pin.py); the barcode search restates
 # helper.py / generate_decoded_lists.py, which cannot be imported here (h5py, distance, scrappy
 # are absent) -- checked against brute force and hand-made cases only.
 # ---------------------------------------------------------------------------------------------

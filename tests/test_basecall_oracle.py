@@ -1,6 +1,7 @@
-"""SURVEY 8(f) row N3 on the CPU: the basecall oracle (PARITY UNPINNED against flappie, see
-oracle/basecall_oracle.c) on hand-computable cases and properties, and the host-side barcode search
-of the package against the oracle's restatement and brute force."""
+"""SURVEY 8(f) row N3 on the CPU: the basecall oracle (oracle/basecall_oracle.c) on hand-computable cases
+and properties, and the host-side barcode search of the package against the oracle's restatement and
+brute force.  The oracle's parity with the compiled flappie -- path, score bits, change positions and
+bases bit for bit -- is pinned in tests/test_flappie_pin.py on the record tests/golden/flappie_ref.npz."""
 import numpy as np
 import pytest
 
