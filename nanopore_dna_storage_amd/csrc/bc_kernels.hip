@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bc_kernels.h"
+#include "seq_bits.h"
 
 namespace lva {
 
@@ -139,10 +140,10 @@ __global__ __launch_bounds__(64) void bc_basecall(const float* __restrict__ post
 }
 
 // grid: x = read, y = pattern (0 start, 1 end, 2 start-rc, 3 end-rc); 256 threads = 256 windows at a time.
-// Edit distance of the barcode (m <= 64 characters) against a window: the bit-vector recurrence of Myers in
-// Hyyro's global-distance form -- column j of the DP matrix is kept as vertical +1 / -1 delta bit masks, the
-// horizontal delta entering row 0 is always +1 (D[0][j] = j), and the score follows bit m-1.  64-bit integer
-// arithmetic only: the value is the same D[m][m] the row-by-row DP of distance.levenshtein produces.
+// Edit distance of the barcode (m <= 64 characters) against a window: one word of seq_bits.h's bit-vector step --
+// column j of the DP matrix is kept as vertical +1 / -1 delta bit masks, the horizontal delta entering row 0 is
+// always +1 (D[0][j] = j), and the score follows bit m-1.  64-bit integer arithmetic only: the value is the same
+// D[m][m] the row-by-row DP of distance.levenshtein produces.
 __global__ __launch_bounds__(256) void bc_search(const char* __restrict__ bases, const int64_t* __restrict__ base_off,
                                                  const int32_t* __restrict__ nbases, BcPatterns pat,
                                                  uint32_t* __restrict__ best) {
@@ -169,20 +170,14 @@ __global__ __launch_bounds__(256) void bc_search(const char* __restrict__ bases,
   }
   for (int32_t i = lo + (int32_t)tid; i < hi; i += 256) {
     // unit-cost edit distance of pat[w] and txt[i .. i+m)   (distance.levenshtein, helper.py:183,187)
-    unsigned long long vp = ~0ull, vn = 0ull;
+    uint64_t vp = ~0ull, vn = 0ull, hp, hn;
     uint32_t score = (uint32_t)m;
     for (int32_t j = 0; j < m; ++j) {
       const char ch = txt[i + j];
-      const unsigned long long eq = ch == 'A' ? peq0 : ch == 'C' ? peq1 : ch == 'G' ? peq2 : ch == 'T' ? peq3 : 0ull;
-      const unsigned long long x = eq | vn;
-      const unsigned long long d0 = ((vp + (x & vp)) ^ vp) | x;
-      const unsigned long long hn = vp & d0;
-      const unsigned long long hp = vn | ~(vp | d0);
+      const uint64_t eq = ch == 'A' ? peq0 : ch == 'C' ? peq1 : ch == 'G' ? peq2 : ch == 'T' ? peq3 : 0ull;
+      bv_step_word(vp, vn, eq, 1, hp, hn);
       score += (hp & top) ? 1u : 0u;
       score -= (hn & top) ? 1u : 0u;
-      const unsigned long long xs = (hp << 1) | 1ull;
-      vn = xs & d0;
-      vp = (hn << 1) | ~(xs | d0);
     }
     const uint32_t k = (score << 20) | (uint32_t)(i - lo);
     key = k < key ? k : key;                             // smallest distance, then first index (:190-191)
@@ -312,25 +307,19 @@ __global__ __launch_bounds__(256) void bc_search_multi(const char* __restrict__ 
       const unsigned long long peq0 = s_peq[j][0], peq1 = s_peq[j][1], peq2 = s_peq[j][2], peq3 = s_peq[j][3];
       const unsigned long long top = 1ull << (m - 1);
       // unit-cost edit distance of pattern j and txt[i .. i+m): the recurrence of bc_search
-      unsigned long long vp = ~0ull, vn = 0ull;
+      uint64_t vp = ~0ull, vn = 0ull, hp, hn;
       uint32_t score = (uint32_t)m;
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         uint32_t cw = code[g], vw = valid[g];
         const int32_t cnt = m - 16 * g < 16 ? m - 16 * g : 16;
         for (int32_t k = 0; k < cnt; ++k) {
-          const unsigned long long sel = (cw & 2u) ? ((cw & 1u) ? peq3 : peq2) : ((cw & 1u) ? peq1 : peq0);
-          const unsigned long long eq = (vw & 1u) ? sel : 0ull;
+          const uint64_t sel = (cw & 2u) ? ((cw & 1u) ? peq3 : peq2) : ((cw & 1u) ? peq1 : peq0);
+          const uint64_t eq = (vw & 1u) ? sel : 0ull;
           cw >>= 2; vw >>= 1;
-          const unsigned long long x = eq | vn;
-          const unsigned long long d0 = ((vp + (x & vp)) ^ vp) | x;
-          const unsigned long long hn = vp & d0;
-          const unsigned long long hp = vn | ~(vp | d0);
+          bv_step_word(vp, vn, eq, 1, hp, hn);
           score += (hp & top) ? 1u : 0u;
           score -= (hn & top) ? 1u : 0u;
-          const unsigned long long xs = (hp << 1) | 1ull;
-          vn = xs & d0;
-          vp = (hn << 1) | ~(xs | d0);
         }
       }
       uint32_t key = mine ? (score << 20) | (uint32_t)(i - lo) : kBcNone;    // smallest distance, then first index (:190-191)

@@ -8,10 +8,10 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "seq_bits.h"
+
 namespace lva {
 
-constexpr int kEpMaxRef = 1024;        // reference positions (the simulator's strand limit)
-constexpr int kEpMaxRead = 4096;       // bases of a read window
 constexpr int kEpStripe = 64;          // reference rows a wavefront fills at a time
 
 // Bytes of move codes that ep_fill writes for a read of n bases against ref_len positions: per stripe of 64 rows one

@@ -28,24 +28,11 @@ namespace lva {
 namespace {
 
 constexpr int kMoveDiag = 0, kMoveUp = 1, kMoveLeft = 2;
-constexpr uint32_t kBaseN = 4;
 
-// basecall characters and lva_encode's codes -> 0..3, anything else N
-__device__ __forceinline__ uint32_t base_code(uint8_t b) {
-  switch (b) {
-    case 'A': case 0: return 0;
-    case 'C': case 1: return 1;
-    case 'G': case 2: return 2;
-    case 'T': case 3: return 3;
-    default: return kBaseN;
-  }
-}
-
-// base j (from 0) of the window w of n bytes as it is aligned: reverse-complemented if flip, N stays N
+// base j (from 0) of the window w of n bytes as it is aligned: reverse-complemented if flip
 __device__ __forceinline__ uint32_t read_base(const uint8_t* w, int n, int j, bool flip) {
   if (!flip) return base_code(w[j]);
-  const uint32_t c = base_code(w[n - 1 - j]);
-  return c < kBaseN ? 3u - c : kBaseN;
+  return complement_code(base_code(w[n - 1 - j]));
 }
 
 // N equals nothing, itself included
@@ -56,8 +43,8 @@ __global__ __launch_bounds__(64) void ep_fill(const uint8_t* __restrict__ bases,
                                               const int32_t* __restrict__ n_bases, const uint8_t* __restrict__ refs, int ref_len,
                                               const int32_t* __restrict__ ref_id, const uint8_t* __restrict__ rc,
                                               const int64_t* __restrict__ move_off, uint8_t* __restrict__ moves) {
-  __shared__ uint8_t rd[kEpMaxRead];                     // the window as it is aligned, 0..4
-  __shared__ uint16_t row[2][kEpMaxRead + 1];            // D[64 s][0 .. n]: the row above stripe s, and the one it leaves
+  __shared__ uint8_t rd[kMaxRead];                       // the window as it is aligned, 0..4
+  __shared__ uint16_t row[2][kMaxRead + 1];              // D[64 s][0 .. n]: the row above stripe s, and the one it leaves
   const int lane = threadIdx.x;
   const size_t r = blockIdx.x;
   const int id = ref_id[r], n = n_bases[r];

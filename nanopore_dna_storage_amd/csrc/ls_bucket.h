@@ -1,5 +1,6 @@
-// ls_bucket.h -- the listing step the per-index kernels share: ls_consensus (ls_kernels.hip) lists and votes in one
-// launch, tr_bucket_list (tr_kernels.hip) lists once for the many trials that vote afterwards.
+// ls_bucket.h -- what the per-index kernels share: the listing step -- ls_consensus (ls_kernels.hip) lists and votes in
+// one launch, tr_bucket_list (tr_kernels.hip) lists once for the many trials that vote afterwards -- and the comparison
+// of two payloads that both votes count with.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,6 +21,13 @@ __device__ __forceinline__ void list_bucket(const int32_t* __restrict__ index, i
     if (m && at < t) mem[at] = i;
     pos += __popcll(mask);
   }
+}
+
+// what a vote compares: the n payload bytes of two reads
+__device__ __forceinline__ bool same_payload(const uint8_t* a, const uint8_t* b, int n) {
+  for (int k = 0; k < n; ++k)
+    if (a[k] != b[k]) return false;
+  return true;
 }
 
 }  // namespace lva

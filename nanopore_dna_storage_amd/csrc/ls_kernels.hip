@@ -20,6 +20,7 @@
 
 #include "ls_bucket.h"
 #include "ls_kernels.h"
+#include "seq_bits.h"
 
 namespace lva {
 
@@ -117,12 +118,6 @@ __global__ __launch_bounds__(256) void ls_bucket_scan(int32_t* __restrict__ buck
   __syncthreads();
   int run = part[tid];
   for (int i = lo; i < hi; ++i) { const int v = bucket[i]; bucket[i] = run; run += v; }
-}
-
-__device__ __forceinline__ bool same_payload(const uint8_t* a, const uint8_t* b, int n) {
-  for (int k = 0; k < n; ++k)
-    if (a[k] != b[k]) return false;
-  return true;
 }
 
 // grid = indices, block = one wavefront.  The wavefront first lists the reads of its index in read order
@@ -237,40 +232,27 @@ __global__ __launch_bounds__(64) void ls_stats(const uint8_t* __restrict__ msgs,
   }
 }
 
-// Unit-cost Levenshtein distance of two m-bit strings, m <= 64 W: Myers' bit-vector recurrence in Hyyro's form for
-// the whole-string distance (the horizontal delta of row 0 is +1: a 1 is shifted into Ph), on a W-word integer with
-// carries.  a = pattern, b = text, bit i of word k = position 64 k + i; bits past m are zero on entry and never
-// reach the bits below them (carries and shifts only move up).
+// Unit-cost Levenshtein distance of two m-bit strings, m <= 64 W: seq_bits.h's bit-vector step over the W words of a
+// column, for the whole-string distance (the horizontal delta entering row 0 is +1, each word's leaving delta enters
+// the next).  a = pattern, b = text, bit i of word k = position 64 k + i; rows past m take part but never reach the
+// rows below them (deltas and shifts only move up).
 template <int W>
 __device__ __forceinline__ int myers(const unsigned long long* a, const unsigned long long* b, int m) {
-  unsigned long long pv[W], mv[W], tx[W];
+  uint64_t pv[W], mv[W], tx[W];
 #pragma unroll
   for (int k = 0; k < W; ++k) { pv[k] = ~0ull; mv[k] = 0; tx[k] = b[k]; }
-  const int hw = (m - 1) >> 6;
-  const unsigned long long hb = 1ull << ((m - 1) & 63);
+  const int hw = (m - 1) >> 6, hb = (m - 1) & 63;
   int score = m;
   for (int j = 0; j < m; ++j) {
-    const unsigned long long flip = (tx[0] & 1ull) ? 0ull : ~0ull;       // Eq = positions of the pattern equal to text bit j
-    unsigned long long carry = 0, ph_in = 1, mh_in = 0;
+    const uint64_t flip = (tx[0] & 1ull) ? 0ull : ~0ull;                 // Eq = positions of the pattern equal to text bit j
+    int h = 1;
 #pragma unroll
     for (int k = 0; k < W; ++k) {
       if (k + 1 < W) tx[k] = (tx[k] >> 1) | (tx[k + 1] << 63); else tx[k] >>= 1;
-      const unsigned long long eq = a[k] ^ flip;
-      const unsigned long long xv = eq | mv[k];
-      const unsigned long long x = eq & pv[k];
-      const unsigned long long s1 = x + pv[k];
-      const unsigned long long s = s1 + carry;
-      carry = (unsigned long long)(s1 < x) | (unsigned long long)(s < s1);
-      const unsigned long long xh = (s ^ pv[k]) | eq;
-      unsigned long long ph = mv[k] | ~(xh | pv[k]);
-      unsigned long long mh = pv[k] & xh;
-      if (k == hw) score += (int)((ph & hb) != 0) - (int)((mh & hb) != 0);
-      const unsigned long long ph_out = ph >> 63, mh_out = mh >> 63;
-      ph = (ph << 1) | ph_in;
-      mh = (mh << 1) | mh_in;
-      ph_in = ph_out; mh_in = mh_out;
-      pv[k] = mh | ~(xv | ph);
-      mv[k] = ph & xv;
+      const uint64_t eq = a[k] ^ flip;
+      uint64_t ph, mh;
+      h = bv_step_word(pv[k], mv[k], eq, h, ph, mh);
+      if (k == hw) score += bv_row_delta(ph, mh, hb);
     }
   }
   return score;
@@ -313,11 +295,9 @@ int launch_ls_consensus(const int32_t* index, const uint8_t* payload, int32_t n_
                         int32_t num_oligos, int32_t first_only, int32_t* bucket, int32_t* order, uint8_t* present,
                         uint8_t* out_payload, int32_t* votes, void* stream) {
   if (n_reads <= 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(ls_bucket_count, dim3(num_oligos), dim3(64), 0, st, index, n_reads, bucket);
-  hipLaunchKernelGGL(ls_bucket_scan, dim3(1), dim3(256), 0, st, bucket, num_oligos);
-  hipLaunchKernelGGL(ls_consensus, dim3(num_oligos), dim3(64), 0, st, index, payload, n_reads, bytes_per_oligo, first_only, bucket,
-                     order, present, out_payload, votes);
+  if (const int e = launch_ls_bucket_scan(index, n_reads, num_oligos, bucket, stream)) return e;
+  hipLaunchKernelGGL(ls_consensus, dim3(num_oligos), dim3(64), 0, (hipStream_t)stream, index, payload, n_reads, bytes_per_oligo,
+                     first_only, bucket, order, present, out_payload, votes);
   return (int)hipGetLastError();
 }
 

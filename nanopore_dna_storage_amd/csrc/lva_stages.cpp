@@ -193,6 +193,38 @@ Calls given_set(Frame& f, const char* bases, const uint32_t* trans, const int64_
   return {f.in(base_offsets, nb.size() + 1), {}, {}, f.in(bases, T), f.in(trans, T), f.in(nb.data(), nb.size())};
 }
 
+// Windows into a caller's base buffer (read i: bases[first_base[i] .. + n_bases[i]); they may overlap or lie far apart), as
+// the error profile and read mapping take them: checked, packed one after the other, declared on the call's frame.  A
+// call that shortens windows fills nb and packs with it.  Declared before the frame: the uploads read the vectors.
+struct Windows {
+  std::vector<uint8_t> packed;
+  std::vector<int32_t> win_off, nb;
+  Piece<uint8_t> bases;
+  Piece<int32_t> off, len;
+  // everything about n windows that can be refused without the device: a start below 0, a length outside [0, limit], 2^31 bases in all
+  static int check(const int64_t* first_base, const int32_t* n_bases, int32_t n, int32_t limit) {
+    uint64_t sum = 0;
+    for (int32_t i = 0; i < n; ++i) {
+      if (first_base[i] < 0 || n_bases[i] < 0 || n_bases[i] > limit) return LVA_ERR_ARG;
+      sum += (uint64_t)n_bases[i];
+    }
+    return sum >= (1ull << 31) ? LVA_ERR_ARG : LVA_OK;
+  }
+  // lens: n_bases as check() passed them, or nb
+  void pack(Frame& f, const uint8_t* src, const int64_t* first_base, const int32_t* lens, size_t n) {
+    win_off.resize(n);
+    size_t at = 0;
+    for (size_t i = 0; i < n; ++i) { win_off[i] = (int32_t)at; at += (size_t)lens[i]; }
+    packed.resize(at);
+    for (size_t i = 0; i < n; ++i)
+      if (lens[i] > 0) std::memcpy(packed.data() + win_off[i], src + first_base[i], (size_t)lens[i]);
+    bases = f.in(packed.data(), at); off = f.in(win_off.data(), n); len = f.in(lens, n);
+  }
+  // what a launcher takes for the chunk of reads that starts at read a
+  struct Chunk { const uint8_t* bases; const int32_t* off; const int32_t* len; };
+  Chunk from(size_t a) const { return {bases, off.ptr() + a, len.ptr() + a}; }
+};
+
 // bc_basecall over posteriors that are on the device
 int enqueue_basecall(const Frame& f, const Calls& c, const float* post_dev, int32_t n) {
   return launch_status(launch_bc_basecall(post_dev, c.off, n, c.tb, c.path, c.bases, c.trans, c.nb, f.stream()));
@@ -944,21 +976,15 @@ namespace {
 
 constexpr size_t kEpChunkBytes = (size_t)1 << 30;        // what the move codes of a chunk of reads may occupy on the device
 
-// everything lva_align_profile can refuse without the device; *total = bases of the reads that are not skipped
+// everything lva_align_profile can refuse without the device
 int profile_args(const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases, int32_t n_reads, const uint8_t* refs,
-                 int32_t n_refs, int32_t ref_len, const int32_t* ref_id, int32_t chunk_reads, size_t* total) {
+                 int32_t n_refs, int32_t ref_len, const int32_t* ref_id, int32_t chunk_reads) {
   if (n_reads < 0 || chunk_reads < 0 || !refs) return LVA_ERR_ARG;
-  if (ref_len < 1 || ref_len > kEpMaxRef || n_refs < 1 || (uint64_t)n_refs * (uint64_t)ref_len >= (1ull << 31)) return LVA_ERR_ARG;
+  if (ref_len < 1 || ref_len > kMaxRef || n_refs < 1 || (uint64_t)n_refs * (uint64_t)ref_len >= (1ull << 31)) return LVA_ERR_ARG;
   if (n_reads > 0 && (!bases || !first_base || !n_bases || !ref_id)) return LVA_ERR_ARG;
-  uint64_t sum = 0, kept = 0;
-  for (int32_t i = 0; i < n_reads; ++i) {
-    if (first_base[i] < 0 || n_bases[i] < 0 || n_bases[i] > kEpMaxRead || ref_id[i] >= n_refs) return LVA_ERR_ARG;
-    sum += (uint64_t)n_bases[i];
-    if (ref_id[i] >= 0) kept += (uint64_t)n_bases[i];
-  }
-  if (sum >= (1ull << 31)) return LVA_ERR_ARG;
-  *total = (size_t)kept;
-  return LVA_OK;
+  for (int32_t i = 0; i < n_reads; ++i)
+    if (ref_id[i] >= n_refs) return LVA_ERR_ARG;
+  return Windows::check(first_base, n_bases, n_reads, kMaxRead);
 }
 
 }  // namespace
@@ -968,29 +994,26 @@ extern "C" {
 int lva_align_profile(int32_t device, const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases, int32_t n_reads,
                       const uint8_t* refs, int32_t n_refs, int32_t ref_len, const int32_t* ref_id, const uint8_t* rc,
                       int32_t chunk_reads, int32_t* out_read, int64_t* out_pos, int64_t* out_conf, int64_t* out_ins) {
-  size_t total = 0;
-  if (profile_args(bases, first_base, n_bases, n_reads, refs, n_refs, ref_len, ref_id, chunk_reads, &total) != LVA_OK) return LVA_ERR_ARG;
+  if (profile_args(bases, first_base, n_bases, n_reads, refs, n_refs, ref_len, ref_id, chunk_reads) != LVA_OK) return LVA_ERR_ARG;
   if (n_reads == 0) return LVA_OK;
   const size_t n = (size_t)n_reads, np = 4 * ((size_t)ref_len + 1);
-  std::vector<uint8_t> packed, flip;                     // (these outlive the call's frame)
-  std::vector<int32_t> win_off, nb;
+  Windows w;                                             // (these outlive the call's frame)
+  std::vector<uint8_t> flip;
   std::vector<int64_t> move_off, zero;
   Frame f;
   if (const int so = f.open(device)) return so;
-  // the windows of the reads that are not skipped, one after the other (windows may overlap, or lie far apart, in `bases`)
-  packed.resize(total); flip.assign(n, 0);
-  win_off.resize(n); nb.resize(n); move_off.resize(n);
+  // a skipped read has no window: nothing of it is packed
+  w.nb.resize(n);
+  for (size_t i = 0; i < n; ++i) w.nb[i] = ref_id[i] < 0 ? 0 : n_bases[i];
+  w.pack(f, bases, first_base, w.nb.data(), n);
+  flip.assign(n, 0); move_off.resize(n);
   zero.assign(std::max<size_t>(np, 24), 0);
   // chunks: reads [cuts[k], cuts[k + 1]), as many as chunk_reads allows and as fit kEpChunkBytes (one read: at most 4.3 MB)
   std::vector<size_t> cuts{0};
-  size_t at = 0, in_chunk = 0, cap = 0;
+  size_t in_chunk = 0, cap = 0;
   for (size_t i = 0; i < n; ++i) {
-    nb[i] = ref_id[i] < 0 ? 0 : n_bases[i];
-    win_off[i] = (int32_t)at;
-    if (nb[i] > 0) std::memcpy(packed.data() + at, bases + first_base[i], (size_t)nb[i]);
-    at += (size_t)nb[i];
     if (rc && rc[i]) flip[i] = 1;
-    const size_t mb = ep_move_bytes(ref_len, nb[i]);
+    const size_t mb = ep_move_bytes(ref_len, w.nb[i]);
     if (i > cuts.back() && (in_chunk + mb > kEpChunkBytes || (chunk_reads > 0 && i - cuts.back() >= (size_t)chunk_reads))) {
       cuts.push_back(i);
       in_chunk = 0;
@@ -1000,8 +1023,7 @@ int lva_align_profile(int32_t device, const uint8_t* bases, const int64_t* first
     cap = std::max(cap, in_chunk);
   }
   cuts.push_back(n);
-  const auto d_bases = f.in(packed.data(), total);
-  const auto d_win = f.in(win_off.data(), n), d_nb = f.in(nb.data(), n), d_id = f.in(ref_id, n);
+  const auto d_id = f.in(ref_id, n);
   const auto d_flip = f.in(flip.data(), n);
   const auto d_moff = f.in(move_off.data(), n);
   const auto d_refs = f.in(refs, (size_t)n_refs * (size_t)ref_len);
@@ -1012,10 +1034,11 @@ int lva_align_profile(int32_t device, const uint8_t* bases, const int64_t* first
   for (size_t k = 0; k + 1 < cuts.size(); ++k) {         // the tallies are sums over reads: chunks change nothing
     const size_t a = cuts[k];
     const int32_t c = (int32_t)(cuts[k + 1] - a);
-    int e = launch_ep_fill(d_bases, d_win.ptr() + a, d_nb.ptr() + a, c, d_refs, ref_len, d_id.ptr() + a, d_flip.ptr() + a,
-                           d_moff.ptr() + a, d_moves, f.stream());
-    if (!e) e = launch_ep_walk(d_bases, d_win.ptr() + a, d_nb.ptr() + a, c, d_refs, ref_len, d_id.ptr() + a, d_flip.ptr() + a,
-                               d_moff.ptr() + a, d_moves, d_read.ptr() + 4 * a, d_pos, d_conf, d_ins, f.stream());
+    const Windows::Chunk x = w.from(a);
+    int e = launch_ep_fill(x.bases, x.off, x.len, c, d_refs, ref_len, d_id.ptr() + a, d_flip.ptr() + a, d_moff.ptr() + a, d_moves,
+                           f.stream());
+    if (!e) e = launch_ep_walk(x.bases, x.off, x.len, c, d_refs, ref_len, d_id.ptr() + a, d_flip.ptr() + a, d_moff.ptr() + a, d_moves,
+                               d_read.ptr() + 4 * a, d_pos, d_conf, d_ins, f.stream());
     if (e) return launch_status(e);
   }
   return f.finish();
@@ -1039,29 +1062,12 @@ namespace {
 
 constexpr size_t kMpChunkBytes = (size_t)1 << 30;        // what the candidate lists of a chunk of reads may occupy on the device
 
-inline uint32_t mp_base(uint8_t b) {                     // as the kernels read a byte
-  switch (b) {
-    case 'A': case 0: return 0;
-    case 'C': case 1: return 1;
-    case 'G': case 2: return 2;
-    case 'T': case 3: return 3;
-    default: return 4;
-  }
-}
-
-// everything lva_map_reads can refuse without the device; *total = bases of all windows
+// everything lva_map_reads can refuse without the device
 int map_args(const lva_map_index* idx, const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases, int32_t n_reads,
-             int32_t cands, int32_t min_votes, int32_t max_dist, int32_t chunk_reads, const int32_t* out, size_t* total) {
+             int32_t cands, int32_t min_votes, int32_t max_dist, int32_t chunk_reads, const int32_t* out) {
   if (!idx || n_reads < 0 || chunk_reads < 0 || cands < 1 || cands > kMpMaxCands || min_votes < 1 || max_dist < 0) return LVA_ERR_ARG;
   if (n_reads > 0 && (!bases || !first_base || !n_bases || !out)) return LVA_ERR_ARG;
-  uint64_t sum = 0;
-  for (int32_t i = 0; i < n_reads; ++i) {
-    if (first_base[i] < 0 || n_bases[i] < 0 || n_bases[i] > kMpMaxRead) return LVA_ERR_ARG;
-    sum += (uint64_t)n_bases[i];
-  }
-  if (sum >= (1ull << 31)) return LVA_ERR_ARG;
-  *total = (size_t)sum;
-  return LVA_OK;
+  return Windows::check(first_base, n_bases, n_reads, kMaxRead);
 }
 
 }  // namespace
@@ -1069,8 +1075,7 @@ int map_args(const lva_map_index* idx, const uint8_t* bases, const int64_t* firs
 extern "C" {
 
 int lva_map_index_create(const uint8_t* refs, int32_t n_refs, int32_t ref_len, int32_t k, int32_t max_occ, lva_map_index** out) {
-  static_assert(kMpMaxRef == kEpMaxRef && kMpMaxRead == kEpMaxRead, "a mapped window is one lva_align_profile accepts");
-  if (!refs || !out || n_refs < 1 || ref_len < 1 || ref_len > kMpMaxRef || k < kMpMinK || k > kMpMaxK) return LVA_ERR_ARG;
+  if (!refs || !out || n_refs < 1 || ref_len < 1 || ref_len > kMaxRef || k < kMpMinK || k > kMpMaxK) return LVA_ERR_ARG;
   if (max_occ < 1 || max_occ > 65535 || (uint64_t)n_refs * (uint64_t)ref_len >= (1ull << 31)) return LVA_ERR_ARG;
   lva_map_index* x = new (std::nothrow) lva_map_index{};
   if (!x) return LVA_ERR_NOMEM;
@@ -1086,8 +1091,8 @@ int lva_map_index_create(const uint8_t* refs, int32_t n_refs, int32_t ref_len, i
       uint32_t code = 0;
       int run = 0;
       for (size_t i = 0; i < m; ++i) {
-        const uint32_t c = mp_base(ref[i]);
-        if (c < 4) {
+        const uint32_t c = base_code(ref[i]);
+        if (c < kBaseN) {
           code = ((code << 2) | c) & mask;
           ++run;
           x->masks[(((size_t)o * 2 + 0) * 4 + c) * W + (i >> 6)] |= 1ull << (i & 63);
@@ -1139,26 +1144,15 @@ int lva_map_index_info(const lva_map_index* idx, int64_t* kmers, int64_t* pairs,
 
 int lva_map_reads(int32_t device, const lva_map_index* idx, const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases,
                   int32_t n_reads, int32_t cands, int32_t min_votes, int32_t max_dist, int32_t chunk_reads, int32_t* out) {
-  size_t total = 0;
-  if (map_args(idx, bases, first_base, n_bases, n_reads, cands, min_votes, max_dist, chunk_reads, out, &total) != LVA_OK) return LVA_ERR_ARG;
+  if (map_args(idx, bases, first_base, n_bases, n_reads, cands, min_votes, max_dist, chunk_reads, out) != LVA_OK) return LVA_ERR_ARG;
   if (n_reads == 0) return LVA_OK;
   const size_t n = (size_t)n_reads;
-  std::vector<uint8_t> packed;                           // (these outlive the call's frame)
-  std::vector<int32_t> win_off;
+  Windows w;                                             // (outlives the call's frame)
   Frame f;
   if (const int so = f.open(device)) return so;
-  // the windows one after the other (windows may overlap, or lie far apart, in `bases`)
-  packed.resize(total); win_off.resize(n);
-  size_t at = 0;
-  for (size_t i = 0; i < n; ++i) {
-    win_off[i] = (int32_t)at;
-    if (n_bases[i] > 0) std::memcpy(packed.data() + at, bases + first_base[i], (size_t)n_bases[i]);
-    at += (size_t)n_bases[i];
-  }
+  w.pack(f, bases, first_base, n_bases, n);              // every read, as given
   size_t chunk = std::min(n, kMpChunkBytes / (kMpMaxCands * sizeof(uint64_t)));
   if (chunk_reads > 0) chunk = std::min(chunk, (size_t)chunk_reads);
-  const auto d_bases = f.in(packed.data(), total);
-  const auto d_win = f.in(win_off.data(), n), d_nb = f.in(n_bases, n);
   const auto d_off = f.in(idx->offsets.data(), idx->offsets.size());
   const auto d_lists = f.in(idx->lists.data(), idx->lists.size());
   const auto d_masks = f.in(idx->masks.data(), idx->masks.size());
@@ -1167,11 +1161,10 @@ int lva_map_reads(int32_t device, const lva_map_index* idx, const uint8_t* bases
   if (const int st = f.begin()) return st;
   for (size_t a = 0; a < n; a += chunk) {                // a read's row depends on the read alone: chunks change nothing
     const int32_t c = (int32_t)std::min(chunk, n - a);
-    int e = launch_mp_vote(d_bases, d_win.ptr() + a, d_nb.ptr() + a, c, d_off, d_lists, idx->k, idx->n_refs, min_votes, cands, d_cand,
-                           f.stream());
-    if (!e) e = launch_mp_verify(d_bases, d_win.ptr() + a, d_nb.ptr() + a, c, d_cand, d_masks, idx->ref_len, cands, max_dist,
-                                 d_out.ptr() + 8 * a, f.stream());
-    if (!e) e = launch_mp_start(d_bases, d_win.ptr() + a, d_nb.ptr() + a, c, d_masks, idx->ref_len, d_out.ptr() + 8 * a, f.stream());
+    const Windows::Chunk x = w.from(a);
+    int e = launch_mp_vote(x.bases, x.off, x.len, c, d_off, d_lists, idx->k, idx->n_refs, min_votes, cands, d_cand, f.stream());
+    if (!e) e = launch_mp_verify(x.bases, x.off, x.len, c, d_cand, d_masks, idx->ref_len, cands, max_dist, d_out.ptr() + 8 * a, f.stream());
+    if (!e) e = launch_mp_start(x.bases, x.off, x.len, c, d_masks, idx->ref_len, d_out.ptr() + 8 * a, f.stream());
     if (e) return launch_status(e);
   }
   return f.finish();

@@ -1,59 +1,35 @@
 // mp_kernels.h -- launchers of the kernels in mp_kernels.hip: reads mapped to oligos without an index of their own
 // (DESIGN.md section 1, row N6): k-mer votes pick candidate (strand, oligo) pairs, a multi-word bit-vector edit distance
-// with free read ends verifies them, an anchored reverse pass finds where the winner's alignment starts.  The definition
-// is nanopore_dna_storage_amd/read_map.py (reference_map).  All pointers are device pointers.  A call works on a chunk of
-// reads; the per-read arrays start at the chunk's first read.  Every launcher returns a hipError_t as int and launches
-// nothing for n_reads <= 0.
+// with free read ends (the step of seq_bits.h) verifies them, an anchored reverse pass finds where the winner's alignment
+// starts.  The definition is nanopore_dna_storage_amd/read_map.py (reference_map).  All pointers are device pointers.  A
+// call works on a chunk of reads; the per-read arrays start at the chunk's first read.  Every launcher returns a
+// hipError_t as int and launches nothing for n_reads <= 0.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 
-#ifdef __HIP__
-#define MP_HD __host__ __device__
-#else
-#define MP_HD
-#endif
+#include "seq_bits.h"
 
 namespace lva {
 
 constexpr int kMpMinK = 6, kMpMaxK = 12;   // bases of a k-mer: the direct table has 4^k + 1 offsets
-constexpr int kMpMaxRef = 1024;            // oligo positions (ep_kernels.h's limit)
-constexpr int kMpMaxRead = 4096;           // bases of a read window
 constexpr int kMpMaxCands = 8;             // candidates a read may keep
-constexpr int kMpMaxWords = 16;            // 64-row words of an oligo: kMpMaxRef / 64
+constexpr int kMpMaxWords = kMaxRef / 64;  // 64-row words of an oligo
 constexpr int kMpVoteThreads = 256;
 // Oligos whose votes one pass of mp_vote counts in LDS (read_map.VOTE_RANGE; tests/test_read_map_host.py holds the two
 // equal): one experiment -- at most 4096 oligos, the 12-bit index -- takes a single pass.
 constexpr int kMpVoteRange = 4096;
 // LDS of mp_vote: the window as codes, uint16 counters [2][kMpVoteRange], the running top list, one minimum per wavefront
-constexpr int kMpVoteLdsBytes = kMpMaxRead + 4 * kMpVoteRange + 8 * kMpMaxCands + 8 * (kMpVoteThreads / 64);
+constexpr int kMpVoteLdsBytes = kMaxRead + 4 * kMpVoteRange + 8 * kMpMaxCands + 8 * (kMpVoteThreads / 64);
 
 constexpr uint64_t kMpNoCand = ~0ull;
 // The order of the candidates as one integer, smaller first: votes descending, strand ascending, oligo ascending.
-MP_HD inline uint64_t mp_cand_key(uint32_t votes, uint32_t strand, uint32_t oligo) {
+SEQ_HD inline uint64_t mp_cand_key(uint32_t votes, uint32_t strand, uint32_t oligo) {
   return ((uint64_t)(0xFFFFu - votes) << 32) | ((uint64_t)strand << 31) | (uint64_t)oligo;
 }
-MP_HD inline int32_t mp_key_votes(uint64_t key) { return (int32_t)(0xFFFFu - (uint32_t)(key >> 32)); }
-MP_HD inline int32_t mp_key_strand(uint64_t key) { return (int32_t)((key >> 31) & 1u); }
-MP_HD inline int32_t mp_key_oligo(uint64_t key) { return (int32_t)(key & 0x7FFFFFFFu); }
-
-// One column of the unit-cost matrix over 64 rows (Myers' bit-vector recurrence in its block form): pv / mv are the
-// vertical +1 / -1 deltas of the column, eq the rows whose oligo base equals the column's read base, hin the horizontal
-// delta entering the word's first row (-1, 0, +1).  Leaves the next column in pv / mv and the horizontal deltas of the
-// 64 rows in ph / mh; returns the delta leaving the last row, which enters the next word.
-MP_HD inline int mp_step_word(uint64_t& pv, uint64_t& mv, uint64_t eq, int hin, uint64_t& ph, uint64_t& mh) {
-  const uint64_t neg = hin < 0 ? 1ull : 0ull, pos = hin > 0 ? 1ull : 0ull;
-  const uint64_t xv = eq | mv;
-  eq |= neg;
-  const uint64_t xh = (((eq & pv) + pv) ^ pv) | eq;
-  ph = mv | ~(xh | pv);
-  mh = pv & xh;
-  const int hout = (int)(ph >> 63) - (int)(mh >> 63);
-  const uint64_t phs = (ph << 1) | pos, mhs = (mh << 1) | neg;
-  pv = mhs | ~(xv | phs);
-  mv = phs & xv;
-  return hout;
-}
+SEQ_HD inline int32_t mp_key_votes(uint64_t key) { return (int32_t)(0xFFFFu - (uint32_t)(key >> 32)); }
+SEQ_HD inline int32_t mp_key_strand(uint64_t key) { return (int32_t)((key >> 31) & 1u); }
+SEQ_HD inline int32_t mp_key_oligo(uint64_t key) { return (int32_t)(key & 0x7FFFFFFFu); }
 
 // Match masks of an oligo: masks[((oligo * 2 + reversed) * 4 + base) * words + w], bit i of word w set where position
 // 64 w + i of the (reversed) oligo is `base`; rows past ref_len are clear.

@@ -28,19 +28,7 @@ namespace lva {
 
 namespace {
 
-constexpr uint32_t kBaseN = 4;
 constexpr int kTileRow = 17;          // dwords of a tile row: 64 codes and one of padding
-
-// basecall characters and lva_encode's codes -> 0..3, anything else N
-__device__ __forceinline__ uint32_t base_code(uint8_t b) {
-  switch (b) {
-    case 'A': case 0: return 0;
-    case 'C': case 1: return 1;
-    case 'G': case 2: return 2;
-    case 'T': case 3: return 3;
-    default: return kBaseN;
-  }
-}
 
 __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int o) {
   const uint32_t lo = __shfl_xor((uint32_t)v, o), hi = __shfl_xor((uint32_t)(v >> 32), o);
@@ -90,7 +78,7 @@ __global__ __launch_bounds__(kMpVoteThreads) void mp_vote(const uint8_t* __restr
   __shared__ uint64_t top[kMpMaxCands];                        // the first candidates of the ranges so far, in order
   __shared__ uint64_t red[kMpVoteThreads / 64];
   __shared__ uint32_t cnt[2][kMpVoteRange / 2];                // uint16 [2][kMpVoteRange], two counters to a word
-  __shared__ uint8_t rd[kMpMaxRead];                           // the window as given, 0..4
+  __shared__ uint8_t rd[kMaxRead];                             // the window as given, 0..4
   static_assert(sizeof(top) + sizeof(red) + sizeof(cnt) + sizeof(rd) == kMpVoteLdsBytes, "kMpVoteLdsBytes");
   const int tid = threadIdx.x;
   const size_t r = blockIdx.x;
@@ -118,7 +106,7 @@ __global__ __launch_bounds__(kMpVoteThreads) void mp_vote(const uint8_t* __restr
           const uint32_t c = rd[j];
           if (c < kBaseN) {
             fwd = ((fwd << 2) | c) & mask;
-            rev = (rev >> 2) | ((3u - c) << hi_shift);
+            rev = (rev >> 2) | (complement_code(c) << hi_shift);
             ++run;
           } else {
             run = 0;
@@ -168,7 +156,7 @@ __global__ __launch_bounds__(kMpVoteThreads) void mp_vote(const uint8_t* __restr
 }
 
 // WT = 2, 4: the vertical vectors of WT words in registers (ref_len <= 64 WT; words past the oligo's last carry no
-// match and change nothing below them).  WT = 0: any ref_len <= kMpMaxRef, the vectors in LDS.
+// match and change nothing below them).  WT = 0: any ref_len <= kMaxRef, the vectors in LDS.
 // grid = ceil(reads / (64 / L)), block = one wavefront.  anchored = 0: L lanes per read, lane c of a read takes its
 // candidate c.  anchored = 1: L = 1, the winner that the first pass left in `out`.
 template <int WT>
@@ -248,7 +236,7 @@ __global__ __launch_bounds__(64) void mp_verify(const uint8_t* __restrict__ base
       uint32_t code = kBaseN;
       if (t < len) {
         code = base_code(bases[s_off[sl] + ((how & 1) ? -t : t)]);
-        if ((how & 2) && code < kBaseN) code = 3u - code;
+        if ((how & 2) && code < kBaseN) code = complement_code(code);      // (asked for bases only: one select per byte)
       }
       reinterpret_cast<uint8_t*>(tile[sl])[lane] = (uint8_t)code;
     }
@@ -266,16 +254,16 @@ __global__ __launch_bounds__(64) void mp_verify(const uint8_t* __restrict__ base
             for (int w = 0; w < WT; ++w) {
               const uint64_t eq = ch == 0 ? peq[0][w] : ch == 1 ? peq[1][w] : ch == 2 ? peq[2][w] : ch == 3 ? peq[3][w] : 0ull;
               uint64_t ph, mh;
-              h = mp_step_word(pv[w], mv[w], eq, h, ph, mh);
-              if (w == wl) score += (int)((ph >> bit) & 1ull) - (int)((mh >> bit) & 1ull);
+              h = bv_step_word(pv[w], mv[w], eq, h, ph, mh);
+              if (w == wl) score += bv_row_delta(ph, mh, bit);
             }
           } else {
             for (int w = 0; w < W; ++w) {
               uint64_t p = s_pv[w][lane], m = s_mv[w][lane], ph, mh;
               const uint64_t eq = ch < kBaseN ? mrow[ch * W + w] : 0ull;
-              h = mp_step_word(p, m, eq, h, ph, mh);
+              h = bv_step_word(p, m, eq, h, ph, mh);
               s_pv[w][lane] = p; s_mv[w][lane] = m;
-              if (w == wl) score += (int)((ph >> bit) & 1ull) - (int)((mh >> bit) & 1ull);
+              if (w == wl) score += bv_row_delta(ph, mh, bit);
             }
           }
           if (score < best) { best = score; arg = t + 1; }     // the smallest column that attains the minimum

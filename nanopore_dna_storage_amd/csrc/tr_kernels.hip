@@ -47,12 +47,6 @@ __device__ __forceinline__ uint32_t trial_place(uint32_t q, uint32_t n, int h, u
   return x;
 }
 
-__device__ __forceinline__ bool same_payload(const uint8_t* a, const uint8_t* b, int n) {
-  for (int k = 0; k < n; ++k)
-    if (a[k] != b[k]) return false;
-  return true;
-}
-
 __device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
   for (int w = 32; w > 0; w >>= 1) v += __shfl_xor(v, w);

@@ -231,8 +231,8 @@ def test_consensus_equals_the_reference_vote(name):
 # ---- statistics ----
 
 # (191, 192, 193: ls_edit's switch from myers<3> to myers<4>, a full third ballot word; appended, so that the cases drawn for the
-#  lengths before them stay what they were)
-STAT_LENS = [36, 63, 64, 65, 128, 129, 180, 255, 191, 192, 193]
+#  lengths before them stay what they were; 127: with 63 .. 65 and 128, 129 both sides of every word boundary of ls_edit's step)
+STAT_LENS = [36, 63, 64, 65, 128, 129, 180, 255, 191, 192, 193, 127]
 
 
 def _blocks(a, b, w):

@@ -218,9 +218,11 @@ def test_declarations():
 def test_vote_range_equals_the_header():
     with open(os.path.join(CSRC, "mp_kernels.h")) as f:
         text = f.read()
+    with open(os.path.join(CSRC, "seq_bits.h")) as f:                              # the limits every sequence stage shares
+        text += f.read()
     const = lambda name: int(re.search(r"constexpr int %s = (\d+);" % name, text).group(1))
     assert rm.VOTE_RANGE == const("kMpVoteRange") >= 4096                          # one experiment, one pass
-    assert rm.MAX_CANDS == const("kMpMaxCands") and const("kMpMaxRef") == MAX_REF and const("kMpMaxRead") == MAX_READ
+    assert rm.MAX_CANDS == const("kMpMaxCands") and const("kMaxRef") == MAX_REF and const("kMaxRead") == MAX_READ
     assert re.search(r"kMpMinK = (\d+), kMpMaxK = (\d+)", text).groups() == tuple(str(v) for v in rm.K_RANGE)
 
 
