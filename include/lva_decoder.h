@@ -109,7 +109,7 @@ const char *lva_version(void);
 /* LVA_ABI_VERSION of the library that was loaded.  It changes whenever a struct of this header changes size or layout
  * (5: lva_profile gained overflow_steps and working_bytes): a caller built against another value must not pass structs.
  * Entry points added since (lva_stream_*, lva_transpost_*, lva_device_download, lva_list_*, lva_demux_*, lva_kernel_plan,
- * lva_align_profile, lva_map_index_*, lva_map_reads) change no struct and keep it at 5. */
+ * lva_align_profile, lva_map_index_*, lva_map_reads, lva_map_reads_pooled) change no struct and keep it at 5. */
 #define LVA_ABI_VERSION 5
 int lva_abi_version(void);
 const char *lva_strerror(int code);
@@ -613,8 +613,27 @@ int lva_align_profile(int32_t device, const uint8_t *bases, const int64_t *first
  * ref_len < 2^31.  lva_map_reads: 1 <= cands <= 8, min_votes >= 1, max_dist >= 0, 0 <= n_bases[i] <= 4096, first_base[i] >=
  * 0, the sum of n_bases below 2^31; chunk_reads reads at a time on the device (0: as many as fit 1 GiB of candidate lists),
  * the result does not depend on it.  Arguments first (LVA_ERR_ARG), then n_reads = 0 succeeds, then the device.
+ *
+ * A pooled run (merged.fa holds the oligos of every experiment, 108 .. 119 bases): one index over oligos of any lengths,
+ * one call for the whole pool.  lva_map_index_create_pooled: oligo o is refs[ref_off[o] .. ref_off[o + 1]); ref_off[0] =
+ * 0, ascending, every length in 1 .. 1024, ref_off[n_refs] < 2^31; an oligo shorter than k contributes no k-mer.
+ * lva_map_index_create builds the same index for equal lengths.  lva_map_reads refuses an index whose oligos differ in
+ * length (LVA_ERR_ARG); lva_map_reads_pooled takes every index: D has rows 0 .. len[o], distances of oligos of different
+ * lengths are compared as they are, ref = best if dist <= max_dist[best] (max_dist [n_refs], each >= 0).  With every
+ * max_dist equal and min_flank = 0 it returns what lva_map_reads returns.
+ *   supplementary pass (min_flank > 0; 0: none, supp is not touched)   of a read with ref >= 0 the longer of the flanks
+ *            [0, start) and [start + count, n) of its window, the left one on a tie, if it has at least min_flank bases, is
+ *            mapped as a read of its own with the same parameters; supp [n_reads][8] is that mapping's row, its start in
+ *            the coordinates of the read's window, and (-1, -1, 0, -1, 0, 0, 0, -1) where there was no pass.  A read whose
+ *            supp row has ref >= 0 is chimeric: two oligos in one read.
  * ------------------------------------------------------------------------------------------- */
 typedef struct lva_map_index lva_map_index;
+int lva_map_index_create_pooled(const uint8_t *refs, const int64_t *ref_off /* [n_refs + 1] */, int32_t n_refs,
+                                int32_t k, int32_t max_occ, lva_map_index **out);
+int lva_map_reads_pooled(int32_t device, const lva_map_index *idx, const uint8_t *bases, const int64_t *first_base,
+                         const int32_t *n_bases, int32_t n_reads, int32_t cands, int32_t min_votes,
+                         const int32_t *max_dist /* [n_refs] */, int32_t min_flank, int32_t chunk_reads,
+                         int32_t *out /* [n_reads][8] */, int32_t *supp /* [n_reads][8]; may be null iff min_flank == 0 */);
 int lva_map_index_create(const uint8_t *refs, int32_t n_refs, int32_t ref_len, int32_t k, int32_t max_occ, lva_map_index **out);
 void lva_map_index_destroy(lva_map_index *idx);
 /* kept distinct k-mers, kept pairs, k-mers dropped by max_occ; each output may be NULL */

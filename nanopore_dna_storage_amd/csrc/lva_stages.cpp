@@ -16,6 +16,7 @@
 #include "tr_kernels.h"
 #include "ep_kernels.h"
 #include "mp_kernels.h"
+#include "mq_kernels.h"
 
 using namespace lva;
 
@@ -1051,10 +1052,12 @@ int lva_align_profile(int32_t device, const uint8_t* bases, const int64_t* first
 // built on the host once and owned by the caller; a mapping call takes a device ordinal like the list consumers.
 // ---------------------------------------------------------------------------------------------
 struct lva_map_index {
-  int32_t n_refs, ref_len, k, max_occ;
+  int32_t n_refs, ref_len, k, max_occ;   // ref_len: the longest oligo; every oligo's where ragged is not set
+  bool ragged;                           // the oligos differ in length: lva_map_reads_pooled alone takes the index
+  std::vector<int32_t> lens;             // [n_refs]
   std::vector<uint32_t> offsets;         // [4^k + 1]: the oligos of k-mer c are lists[offsets[c] .. offsets[c + 1])
   std::vector<int32_t> lists;            // ascending inside a k-mer
-  std::vector<uint64_t> masks;           // mp_mask_words: per oligo, forward and reversed, per base, W words
+  std::vector<uint64_t> masks;           // mp_mask_words(n_refs, ref_len): per oligo, forward and reversed within its own length, per base, W words
   int64_t kmers, pairs, dropped;         // kept distinct k-mers, kept pairs, k-mers that max_occ dropped
 };
 
@@ -1070,24 +1073,34 @@ int map_args(const lva_map_index* idx, const uint8_t* bases, const int64_t* firs
   return Windows::check(first_base, n_bases, n_reads, kMaxRead);
 }
 
-}  // namespace
+// everything lva_map_reads_pooled can refuse without the device
+int map_pooled_args(const lva_map_index* idx, const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases, int32_t n_reads,
+                    int32_t cands, int32_t min_votes, const int32_t* max_dist, int32_t min_flank, int32_t chunk_reads, const int32_t* out,
+                    const int32_t* supp) {
+  if (!idx || n_reads < 0 || chunk_reads < 0 || cands < 1 || cands > kMpMaxCands || min_votes < 1 || min_flank < 0 || !max_dist) return LVA_ERR_ARG;
+  for (int32_t o = 0; o < idx->n_refs; ++o)
+    if (max_dist[o] < 0) return LVA_ERR_ARG;
+  if (n_reads > 0 && (!bases || !first_base || !n_bases || !out || (min_flank > 0 && !supp))) return LVA_ERR_ARG;
+  return Windows::check(first_base, n_bases, n_reads, kMaxRead);
+}
 
-extern "C" {
-
-int lva_map_index_create(const uint8_t* refs, int32_t n_refs, int32_t ref_len, int32_t k, int32_t max_occ, lva_map_index** out) {
-  if (!refs || !out || n_refs < 1 || ref_len < 1 || ref_len > kMaxRef || k < kMpMinK || k > kMpMaxK) return LVA_ERR_ARG;
-  if (max_occ < 1 || max_occ > 65535 || (uint64_t)n_refs * (uint64_t)ref_len >= (1ull << 31)) return LVA_ERR_ARG;
+// THE index builder: oligo o is refs[ref_off[o] .. ref_off[o + 1]), its length in 1 .. kMaxRef (the callers have checked)
+int build_map_index(const uint8_t* refs, const int64_t* ref_off, int32_t n_refs, int32_t k, int32_t max_occ, lva_map_index** out) {
   lva_map_index* x = new (std::nothrow) lva_map_index{};
   if (!x) return LVA_ERR_NOMEM;
   try {
-    x->n_refs = n_refs; x->ref_len = ref_len; x->k = k; x->max_occ = max_occ;
-    const size_t m = (size_t)ref_len, W = (m + 63) / 64, table = (size_t)1 << (2 * k);
+    x->n_refs = n_refs; x->k = k; x->max_occ = max_occ;
+    x->lens = read_lengths(ref_off, n_refs);
+    x->ref_len = *std::max_element(x->lens.begin(), x->lens.end());
+    x->ragged = *std::min_element(x->lens.begin(), x->lens.end()) != x->ref_len;
+    const size_t W = ((size_t)x->ref_len + 63) / 64, table = (size_t)1 << (2 * k);
     // the distinct pairs (k-mer, oligo), k-mer major
     std::vector<uint64_t> pairs;
     const uint32_t mask = (uint32_t)(table - 1);
-    x->masks.assign(mp_mask_words(n_refs, ref_len), 0);
+    x->masks.assign(mp_mask_words(n_refs, x->ref_len), 0);
     for (int32_t o = 0; o < n_refs; ++o) {
-      const uint8_t* ref = refs + (size_t)o * m;
+      const uint8_t* ref = refs + ref_off[o];
+      const size_t m = (size_t)x->lens[o];
       uint32_t code = 0;
       int run = 0;
       for (size_t i = 0; i < m; ++i) {
@@ -1132,6 +1145,32 @@ int lva_map_index_create(const uint8_t* refs, int32_t n_refs, int32_t ref_len, i
   return LVA_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int lva_map_index_create(const uint8_t* refs, int32_t n_refs, int32_t ref_len, int32_t k, int32_t max_occ, lva_map_index** out) {
+  if (!refs || !out || n_refs < 1 || ref_len < 1 || ref_len > kMaxRef || k < kMpMinK || k > kMpMaxK) return LVA_ERR_ARG;
+  if (max_occ < 1 || max_occ > 65535 || (uint64_t)n_refs * (uint64_t)ref_len >= (1ull << 31)) return LVA_ERR_ARG;
+  try {                                  // the equal-length case of the pooled index
+    std::vector<int64_t> ref_off((size_t)n_refs + 1);
+    for (int32_t o = 0; o <= n_refs; ++o) ref_off[o] = (int64_t)o * ref_len;
+    return build_map_index(refs, ref_off.data(), n_refs, k, max_occ, out);
+  } catch (const std::bad_alloc&) {
+    return LVA_ERR_NOMEM;
+  }
+}
+
+int lva_map_index_create_pooled(const uint8_t* refs, const int64_t* ref_off, int32_t n_refs, int32_t k, int32_t max_occ,
+                                lva_map_index** out) {
+  if (!refs || !ref_off || !out || n_refs < 1 || k < kMpMinK || k > kMpMaxK || max_occ < 1 || max_occ > 65535) return LVA_ERR_ARG;
+  size_t total;
+  if (check_offsets(ref_off, n_refs, &total) != LVA_OK) return LVA_ERR_ARG;
+  for (int32_t o = 0; o < n_refs; ++o)
+    if (ref_off[o + 1] - ref_off[o] < 1 || ref_off[o + 1] - ref_off[o] > kMaxRef) return LVA_ERR_ARG;
+  return build_map_index(refs, ref_off, n_refs, k, max_occ, out);
+}
+
 void lva_map_index_destroy(lva_map_index* idx) { delete idx; }
 
 int lva_map_index_info(const lva_map_index* idx, int64_t* kmers, int64_t* pairs, int64_t* dropped_kmers) {
@@ -1145,6 +1184,7 @@ int lva_map_index_info(const lva_map_index* idx, int64_t* kmers, int64_t* pairs,
 int lva_map_reads(int32_t device, const lva_map_index* idx, const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases,
                   int32_t n_reads, int32_t cands, int32_t min_votes, int32_t max_dist, int32_t chunk_reads, int32_t* out) {
   if (map_args(idx, bases, first_base, n_bases, n_reads, cands, min_votes, max_dist, chunk_reads, out) != LVA_OK) return LVA_ERR_ARG;
+  if (idx->ragged) return LVA_ERR_ARG;                    // one ref_len for all: lva_map_reads_pooled takes the others
   if (n_reads == 0) return LVA_OK;
   const size_t n = (size_t)n_reads;
   Windows w;                                             // (outlives the call's frame)
@@ -1165,6 +1205,51 @@ int lva_map_reads(int32_t device, const lva_map_index* idx, const uint8_t* bases
     int e = launch_mp_vote(x.bases, x.off, x.len, c, d_off, d_lists, idx->k, idx->n_refs, min_votes, cands, d_cand, f.stream());
     if (!e) e = launch_mp_verify(x.bases, x.off, x.len, c, d_cand, d_masks, idx->ref_len, cands, max_dist, d_out.ptr() + 8 * a, f.stream());
     if (!e) e = launch_mp_start(x.bases, x.off, x.len, c, d_masks, idx->ref_len, d_out.ptr() + 8 * a, f.stream());
+    if (e) return launch_status(e);
+  }
+  return f.finish();
+}
+
+int lva_map_reads_pooled(int32_t device, const lva_map_index* idx, const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases,
+                         int32_t n_reads, int32_t cands, int32_t min_votes, const int32_t* max_dist, int32_t min_flank,
+                         int32_t chunk_reads, int32_t* out, int32_t* supp) {
+  if (map_pooled_args(idx, bases, first_base, n_bases, n_reads, cands, min_votes, max_dist, min_flank, chunk_reads, out, supp) != LVA_OK)
+    return LVA_ERR_ARG;
+  if (n_reads == 0) return LVA_OK;
+  const size_t n = (size_t)n_reads, nr = (size_t)idx->n_refs;
+  const bool flanks = min_flank > 0;
+  Windows w;                                             // (outlives the call's frame)
+  Frame f;
+  if (const int so = f.open(device)) return so;
+  w.pack(f, bases, first_base, n_bases, n);              // every read, as given
+  size_t chunk = std::min(n, kMpChunkBytes / (kMpMaxCands * sizeof(uint64_t)));
+  if (chunk_reads > 0) chunk = std::min(chunk, (size_t)chunk_reads);
+  const auto d_off = f.in(idx->offsets.data(), idx->offsets.size());
+  const auto d_lists = f.in(idx->lists.data(), idx->lists.size());
+  const auto d_masks = f.in(idx->masks.data(), idx->masks.size());
+  const auto d_lens = f.in(idx->lens.data(), nr);
+  const auto d_max = f.in(max_dist, nr);
+  const auto d_cand = f.scratch<uint64_t>(chunk * kMpMaxCands);
+  const auto d_out = f.out(out, 8 * n);
+  // the supplementary pass: per read of a chunk its flank as a window (offset, length) and the flank's place in the read's window
+  const auto d_supp = flanks ? f.out(supp, 8 * n) : Piece<int32_t>{};
+  const auto d_foff = f.scratch<int32_t>(flanks ? chunk : 0), d_flen = f.scratch<int32_t>(flanks ? chunk : 0);
+  const auto d_fshift = f.scratch<int32_t>(flanks ? chunk : 0);
+  if (const int st = f.begin()) return st;
+  for (size_t a = 0; a < n; a += chunk) {                // a read's rows depend on the read alone: chunks change nothing
+    const int32_t c = (int32_t)std::min(chunk, n - a);
+    const Windows::Chunk x = w.from(a);
+    int32_t* o = d_out.ptr() + 8 * a;
+    int e = launch_mp_vote(x.bases, x.off, x.len, c, d_off, d_lists, idx->k, idx->n_refs, min_votes, cands, d_cand, f.stream());
+    if (!e) e = launch_mq_verify(x.bases, x.off, x.len, c, d_cand, d_masks, d_lens, idx->ref_len, cands, d_max, o, f.stream());
+    if (!e) e = launch_mq_start(x.bases, x.off, x.len, c, d_masks, d_lens, idx->ref_len, nullptr, o, f.stream());
+    if (!e && flanks) {
+      int32_t* s = d_supp.ptr() + 8 * a;
+      e = launch_mq_flank(x.off, x.len, c, o, min_flank, d_foff, d_flen, d_fshift, f.stream());
+      if (!e) e = launch_mp_vote(x.bases, d_foff, d_flen, c, d_off, d_lists, idx->k, idx->n_refs, min_votes, cands, d_cand, f.stream());
+      if (!e) e = launch_mq_verify(x.bases, d_foff, d_flen, c, d_cand, d_masks, d_lens, idx->ref_len, cands, d_max, s, f.stream());
+      if (!e) e = launch_mq_start(x.bases, d_foff, d_flen, c, d_masks, d_lens, idx->ref_len, d_fshift, s, f.stream());
+    }
     if (e) return launch_status(e);
   }
   return f.finish();

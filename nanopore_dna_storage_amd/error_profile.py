@@ -228,23 +228,47 @@ def profile_decoded(dec, dev, off, located_results, filter_index, oligos, device
                          device=dec.device if device is None else device)
 
 
-def profile_mapped(dec, dev, off, index, cands=4, min_votes=2, max_dist=None, device=None):
+def profile_mapped(dec, dev, off, index, cands=4, min_votes=2, max_dist=None, device=None, min_flank=0):
     """The profile of reads that name no oligo: one basecall_resident call over a resident posterior buffer (dev, off), the
     whole basecalls mapped to the oligos of `index` (a read_map.MapIndex; read_map.map_reads), and the mapped parts aligned to
     the oligo and on the strand the mapping found.  No list is decoded and no barcode is looked for, so reads whose list
-    failed the CRC are counted.  -> (ErrorProfile, read_map.MapResult)"""
+    failed the CRC are counted.  -> (ErrorProfile, read_map.MapResult).  An index with groups (a pooled run): one profile per
+    group, over the reads mapped to the group and not chimeric (min_flank: read_map's supplementary pass), each one
+    align_profile call; the oligos of a group are equally long.  -> ([ErrorProfile per group], read_map.MapResult)"""
     from . import read_map
     device = dec.device if device is None else device
     calls = [b for b, _ in dec.basecall_resident(dev, off)]
     bases, win = "".join(calls), read_map.whole_windows(calls)
-    res = read_map.map_reads(bases, win, index, cands, min_votes, max_dist, device=device)
-    return align_profile(bases, res.windows(win), index.refs, res.ref, res.rc, device=device), res
+    res = read_map.map_reads(bases, win, index, cands, min_votes, max_dist, device=device, min_flank=min_flank)
+    if index.groups is None:
+        if index.ragged:
+            raise ValueError("oligos of unequal length: give the index groups of equally long oligos")
+        return align_profile(bases, res.windows(win), index.refs, res.ref, res.rc, device=device), res
+    return [align_profile(bases, res.windows(win), refs, ref_id, res.rc, device=device)
+            for refs, ref_id in group_references(index, res)], res
+
+
+def group_references(index, res):
+    """per group of a read_map.MapIndex with groups: (the group's oligos [n, len], per read the place of its oligo among them,
+    -1 for a read that is unmapped, chimeric or of another group) -- the refs and ref_id of one align_profile call"""
+    group = np.where(res.chimeric, -1, res.group)
+    parts = []
+    for g in range(int(index.groups.max()) + 1):
+        members = np.nonzero(index.groups == g)[0]
+        if not len(members) or len(set(index.lens[members].tolist())) != 1:
+            raise ValueError("group %d holds no oligo, or oligos of unequal length: a profile is per oligo position" % g)
+        place = np.full(index.n_refs, -1, np.int32)
+        place[members] = np.arange(len(members), dtype=np.int32)
+        parts.append((np.stack([index.oligos[o] for o in members]), np.where(group == g, place[np.maximum(res.ref, 0)], -1).astype(np.int32)))
+    return parts
 
 
 def build_parser():
     p = argparse.ArgumentParser(description="error profile of basecalled reads against their oligos: locate, decode, filter, "
                                             "align, <out_prefix>.error_stats.csv")
-    p.add_argument("--oligos", type=str, required=True, help="the oligo file of helper.encode: one ACGT string per line")
+    p.add_argument("--oligos", type=str, required=True, nargs="+",
+                   help="the oligo file of helper.encode: one ACGT string per line; several files (--assign map only): a pooled "
+                        "run, one group and one <out_prefix>.<stem>.error_stats.csv per file")
     p.add_argument("--post_manifest", type=str, required=True, help="readid <TAB> ref <TAB> post_path per read (generate_decoded_lists)")
     p.add_argument("--start_barcode", type=str, required=True)
     p.add_argument("--end_barcode", type=str, required=True)
@@ -267,7 +291,11 @@ def main(argv=None, out=sys.stdout, decoder=None):
     from . import helper, list_ops
     from .decoder import Decoder
     a = build_parser().parse_args(argv)
-    with open(a.oligos) as f:
+    if len(a.oligos) > 1:
+        if a.assign != "map":
+            raise SystemExit("several --oligos files (a pooled run) need --assign map")
+        return pooled_main(a, out, decoder)
+    with open(a.oligos[0]) as f:
         oligos = [ln.strip() for ln in f if ln.strip()]
     with open(a.post_manifest) as f:
         paths = [ln.rstrip("\n").split("\t")[2] for ln in f if ln.strip()]
@@ -306,6 +334,38 @@ def main(argv=None, out=sys.stdout, decoder=None):
     print(*counted, "aligned:", total.reads, file=out)
     print("sub %.6f dele %.6f ins %.6f per reference base" % (r["sub"], r["dele"], r["ins"]), file=out)
     return total
+
+
+def pooled_main(a, out, decoder):
+    """--assign map with several oligo files -> [the ErrorProfile of each group, None where no read was mapped to it]"""
+    from . import helper
+    from .decoder import Decoder
+    from .read_map import MapIndex, read_oligo_files
+    oligos, groups, names = read_oligo_files(a.oligos)
+    with open(a.post_manifest) as f:
+        paths = [ln.rstrip("\n").split("\t")[2] for ln in f if ln.strip()]
+    own = decoder is None
+    dec = Decoder(a.mem_conv, a.rate_conv, a.msg_len, list_size=a.list_size, max_deviation=a.max_deviation, device=a.device) if own else decoder
+    totals, mapped, chimeric = [None] * len(names), 0, 0
+    try:
+        with MapIndex(oligos, groups=groups) as index:
+            for k in range(0, len(paths), max(1, a.chunk)):
+                with dec.resident([helper.read_post_file(p) for p in paths[k:k + max(1, a.chunk)]]) as (dev, off):
+                    parts, res = profile_mapped(dec, dev, off, index, device=a.device, min_flank=int(index.lens.min()) // 2)
+                mapped, chimeric = mapped + res.mapped, chimeric + int(res.chimeric.sum())
+                totals = [p if t is None else t + p for t, p in zip(totals, parts)]
+    finally:
+        if own:
+            dec.close()
+    print("reads:", len(paths), "mapped:", mapped, "chimeric:", chimeric, file=out)
+    for name, total in zip(names, totals):
+        if total is None or total.reads == 0:
+            print(name + ": aligned: 0", file=out)
+            continue
+        total.write_csv(a.out_prefix + "." + name)
+        r = total.rates()
+        print("%s: aligned: %d sub %.6f dele %.6f ins %.6f per reference base" % (name, total.reads, r["sub"], r["dele"], r["ins"]), file=out)
+    return totals
 
 
 if __name__ == "__main__":
