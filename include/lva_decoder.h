@@ -628,6 +628,20 @@ int lva_align_profile(int32_t device, const uint8_t *bases, const int64_t *first
  *            supp row has ref >= 0 is chimeric: two oligos in one read.
  * ------------------------------------------------------------------------------------------- */
 typedef struct lva_map_index lva_map_index;
+/* The same index built on device `device` from the uploaded oligos (csrc/mi_kernels.hip) and resident there until
+ * lva_map_index_destroy: the arguments and refusals of lva_map_index_create_pooled (LVA_ERR_ARG, no device looked for), then
+ * the device (LVA_ERR_NO_DEVICE).  The call waits for the build: the handle is complete when it returns, nothing of the index
+ * is in flight, and a failure leaves *out untouched.  lva_map_reads and lva_map_reads_pooled take such an index with the same
+ * `device` and upload the reads alone, with the results of a host-built index; another `device` is LVA_ERR_ARG.  The build
+ * orders each list by counting, at a cost of the sum of the squared list lengths: meant for max_occ in the hundreds, not for
+ * tens of thousands of oligos that share their k-mers (the host builder sorts and has no such term). */
+int lva_map_index_create_device(int32_t device, const uint8_t *refs, const int64_t *ref_off /* [n_refs + 1] */,
+                                int32_t n_refs, int32_t k, int32_t max_occ, lva_map_index **out);
+/* The tables of an index of either kind, copied to the host -- the same bytes for the same oligos however it was built:
+ * offsets[c] .. offsets[c + 1] bound the oligos of k-mer c in lists, ascending; masks as lva_map_reads reads them, ref_len
+ * the longest oligo.  pairs: lva_map_index_info. */
+int lva_map_index_tables(const lva_map_index *idx, uint32_t *offsets /* [4^k + 1] */, int32_t *lists /* [pairs] */,
+                         uint64_t *masks /* [n_refs * 8 * ceil(ref_len / 64)] */);   /* each may be NULL */
 int lva_map_index_create_pooled(const uint8_t *refs, const int64_t *ref_off /* [n_refs + 1] */, int32_t n_refs,
                                 int32_t k, int32_t max_occ, lva_map_index **out);
 int lva_map_reads_pooled(int32_t device, const lva_map_index *idx, const uint8_t *bases, const int64_t *first_base,

@@ -17,6 +17,7 @@
 #include "ep_kernels.h"
 #include "mp_kernels.h"
 #include "mq_kernels.h"
+#include "mi_kernels.h"
 
 using namespace lva;
 
@@ -62,7 +63,8 @@ int stage_enter(lva_decoder* d, const int64_t* offsets, int32_t n, size_t* total
 
 // What one side-stage call owns on the device: the stream it works on, ONE allocation carved into 256-byte aligned and
 // padded pieces, and the drain.  A piece is declared once, with its host side: in (uploaded by begin), out (copied back by
-// finish; a null host pointer: no copy), inout (both, two host addresses), scratch (neither).  begin() sizes the block from
+// finish; a null host pointer: no copy), inout (both, two host addresses), scratch (neither); resident: device memory that
+// someone else owns and has filled, carried as a piece so that a call reads it like its own.  begin() sizes the block from
 // what was declared and every whole-piece copy takes its bytes from the declaration: neither can disagree with a piece.
 // The destructor drains, then frees, then destroys an owned stream, on every exit.  Host buffers that the copies read or
 // write are declared before the frame, so that they die after it.
@@ -74,7 +76,8 @@ class Frame {
   template <typename T> struct Piece {
     const Frame* f = nullptr;
     size_t at = 0, count = 0;
-    T* ptr() const { return f ? reinterpret_cast<T*>(f->base_ + at) : nullptr; }
+    T* elsewhere = nullptr;                            // resident(): not in the frame's block
+    T* ptr() const { return elsewhere ? elsewhere : f ? reinterpret_cast<T*>(f->base_ + at) : nullptr; }
     operator T*() const { return ptr(); }
   };
   Frame() = default;                                   // a device-ordinal call: open() makes the stream
@@ -105,6 +108,7 @@ class Frame {
   template <typename T> Piece<T> in(const T* src, size_t count) { return inout<T>(src, nullptr, count); }
   template <typename T> Piece<T> out(T* dst, size_t count) { return inout<T>(nullptr, dst, count); }
   template <typename T> Piece<T> scratch(size_t count) { return inout<T>(nullptr, nullptr, count); }
+  template <typename T> Piece<T> resident(const T* dev, size_t count) const { return Piece<T>{nullptr, 0, count, const_cast<T*>(dev)}; }
   int begin() {                                        // allocate, enqueue the uploads
     if (size_ && hipMalloc(reinterpret_cast<void**>(&base_), size_) != hipSuccess) return LVA_ERR_NOMEM;
     for (const Side& x : sides_)
@@ -1049,7 +1053,10 @@ int lva_align_profile(int32_t device, const uint8_t* bases, const int64_t* first
 
 // ---------------------------------------------------------------------------------------------
 // reads mapped to oligos (csrc/mp_kernels.hip; the definition is read_map.py).  The index is
-// built on the host once and owned by the caller; a mapping call takes a device ordinal like the list consumers.
+// built once and owned by the caller; a mapping call takes a device ordinal like the list consumers.  Built on the host
+// (lva_map_index_create, lva_map_index_create_pooled) its tables are host vectors that every mapping call uploads; built on
+// the device (lva_map_index_create_device, csrc/mi_kernels.hip) they are device memory of that ordinal until the index is
+// destroyed, the same bytes, and a mapping call uploads the reads alone.
 // ---------------------------------------------------------------------------------------------
 struct lva_map_index {
   int32_t n_refs, ref_len, k, max_occ;   // ref_len: the longest oligo; every oligo's where ragged is not set
@@ -1059,6 +1066,18 @@ struct lva_map_index {
   std::vector<int32_t> lists;            // ascending inside a k-mer
   std::vector<uint64_t> masks;           // mp_mask_words(n_refs, ref_len): per oligo, forward and reversed within its own length, per base, W words
   int64_t kmers, pairs, dropped;         // kept distinct k-mers, kept pairs, k-mers that max_occ dropped
+  // built on the device: its ordinal (-1: built on the host, the vectors above hold the tables) and the tables there, the
+  // vectors' layouts; d_tables is one allocation (offsets, masks, lens), d_lists its own: its size is known after the scan
+  int32_t device = -1;
+  char* d_tables = nullptr;
+  uint32_t* d_offsets = nullptr;
+  uint64_t* d_masks = nullptr;
+  int32_t* d_lens = nullptr;
+  int32_t* d_lists = nullptr;
+  ~lva_map_index() {                     // hipFree finds the owning device from the pointer: the caller's current device stays
+    if (d_lists) (void)hipFree(d_lists);
+    if (d_tables) (void)hipFree(d_tables);
+  }
 };
 
 namespace {
@@ -1084,15 +1103,29 @@ int map_pooled_args(const lva_map_index* idx, const uint8_t* bases, const int64_
   return Windows::check(first_base, n_bases, n_reads, kMaxRead);
 }
 
-// THE index builder: oligo o is refs[ref_off[o] .. ref_off[o + 1]), its length in 1 .. kMaxRef (the callers have checked)
+// what both builders know before they build: the parameters and the oligos' lengths (may throw bad_alloc)
+void index_shape(lva_map_index* x, const int64_t* ref_off, int32_t n_refs, int32_t k, int32_t max_occ) {
+  x->n_refs = n_refs; x->k = k; x->max_occ = max_occ;
+  x->lens = read_lengths(ref_off, n_refs);
+  x->ref_len = *std::max_element(x->lens.begin(), x->lens.end());
+  x->ragged = *std::min_element(x->lens.begin(), x->lens.end()) != x->ref_len;
+}
+
+// everything the three index entry points can refuse from the offsets
+int index_offsets_args(const int64_t* ref_off, int32_t n_refs) {
+  size_t total;
+  if (check_offsets(ref_off, n_refs, &total) != LVA_OK) return LVA_ERR_ARG;
+  for (int32_t o = 0; o < n_refs; ++o)
+    if (ref_off[o + 1] - ref_off[o] < 1 || ref_off[o + 1] - ref_off[o] > kMaxRef) return LVA_ERR_ARG;
+  return LVA_OK;
+}
+
+// THE host index builder: oligo o is refs[ref_off[o] .. ref_off[o + 1]), its length in 1 .. kMaxRef (the callers have checked)
 int build_map_index(const uint8_t* refs, const int64_t* ref_off, int32_t n_refs, int32_t k, int32_t max_occ, lva_map_index** out) {
   lva_map_index* x = new (std::nothrow) lva_map_index{};
   if (!x) return LVA_ERR_NOMEM;
   try {
-    x->n_refs = n_refs; x->k = k; x->max_occ = max_occ;
-    x->lens = read_lengths(ref_off, n_refs);
-    x->ref_len = *std::max_element(x->lens.begin(), x->lens.end());
-    x->ragged = *std::min_element(x->lens.begin(), x->lens.end()) != x->ref_len;
+    index_shape(x, ref_off, n_refs, k, max_occ);
     const size_t W = ((size_t)x->ref_len + 63) / 64, table = (size_t)1 << (2 * k);
     // the distinct pairs (k-mer, oligo), k-mer major
     std::vector<uint64_t> pairs;
@@ -1145,9 +1178,121 @@ int build_map_index(const uint8_t* refs, const int64_t* ref_off, int32_t n_refs,
   return LVA_OK;
 }
 
+// The same index from the same arguments, built on the device and left there (csrc/mi_kernels.h lists the steps).  Two
+// frames: the first holds the oligos and the counters and ends with the three counts on the host, which size the lists;
+// the second holds the unordered slots and is made only where there are pairs.  x is declared first: the frames drain
+// before its device memory can be freed.
+int build_map_index_device(int32_t device, const uint8_t* refs, const int64_t* ref_off, int32_t n_refs, int32_t k, int32_t max_occ,
+                           lva_map_index** out) {
+  struct Owner {
+    lva_map_index* x;
+    ~Owner() { delete x; }
+  } own{new (std::nothrow) lva_map_index{}};
+  lva_map_index* x = own.x;
+  if (!x) return LVA_ERR_NOMEM;
+  const uint32_t zero[4] = {0, 0, 0, 0};
+  uint32_t stats[4] = {0, 0, 0, 0};                    // kept k-mers, dropped k-mers, pairs
+  try {
+    index_shape(x, ref_off, n_refs, k, max_occ);
+  } catch (const std::bad_alloc&) {
+    return LVA_ERR_NOMEM;
+  }
+  const size_t table = mi_table(k), nr = (size_t)n_refs, words = mp_mask_words(n_refs, x->ref_len);
+  const bool any = x->ref_len >= k;                    // else no oligo holds a k-mer: the table is all zero
+  Frame f;
+  if (const int so = f.open(device)) return so;
+  x->device = device;
+  const auto pad = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+  const size_t at_masks = pad((table + 1) * sizeof(uint32_t)), at_lens = at_masks + pad(words * sizeof(uint64_t));
+  if (hipMalloc(reinterpret_cast<void**>(&x->d_tables), at_lens + pad(nr * sizeof(int32_t))) != hipSuccess) return LVA_ERR_NOMEM;
+  x->d_offsets = reinterpret_cast<uint32_t*>(x->d_tables);
+  x->d_masks = reinterpret_cast<uint64_t*>(x->d_tables + at_masks);
+  x->d_lens = reinterpret_cast<int32_t*>(x->d_tables + at_lens);
+  const auto d_refs = f.in(refs, (size_t)ref_off[n_refs]);
+  const auto d_ref_off = f.in(ref_off, nr + 1);
+  const auto d_counts = f.scratch<uint32_t>(any ? table : 0);
+  const auto d_sums = f.scratch<uint32_t>(any ? mi_scan_tiles(k) : 0);
+  const auto d_stats = f.inout(zero, stats, 4);
+  if (const int st = f.begin()) return st;
+  if (const int st = f.copy(x->d_lens, x->lens.data(), nr * sizeof(int32_t), hipMemcpyHostToDevice)) return st;
+  int e = launch_mi_masks(d_refs, d_ref_off, n_refs, x->ref_len, x->d_masks, f.stream());
+  if (!e && any) {
+    HIP_TRY(hipMemsetAsync(d_counts.ptr(), 0, table * sizeof(uint32_t), f.stream()));
+    e = launch_mi_count(d_refs, d_ref_off, n_refs, k, d_counts, f.stream());
+    if (!e) e = launch_mi_clip(d_counts, k, max_occ, d_stats, f.stream());
+    if (!e) e = launch_mi_scan(d_counts, k, d_sums, x->d_offsets, d_stats, f.stream());
+  } else if (!e) {
+    HIP_TRY(hipMemsetAsync(x->d_offsets, 0, (table + 1) * sizeof(uint32_t), f.stream()));
+  }
+  if (e) return launch_status(e);
+  if (const int st = f.finish()) return st;
+  x->kmers = stats[0]; x->dropped = stats[1]; x->pairs = stats[2];
+  const size_t pairs = (size_t)stats[2];
+  if (hipMalloc(reinterpret_cast<void**>(&x->d_lists), std::max<size_t>(pairs, 1) * sizeof(int32_t)) != hipSuccess) return LVA_ERR_NOMEM;
+  if (pairs) {
+    Frame g;
+    if (const int so = g.open(device)) return so;
+    const auto d_slot_oligo = g.scratch<int32_t>(pairs);
+    const auto d_slot_kmer = g.scratch<uint32_t>(pairs);
+    if (const int st = g.begin()) return st;
+    e = launch_mi_fill(d_refs, d_ref_off, n_refs, k, x->d_offsets, d_counts, d_slot_oligo, d_slot_kmer, g.stream());
+    if (!e) e = launch_mi_rank(d_slot_oligo, d_slot_kmer, (uint32_t)pairs, k, x->d_offsets, x->d_lists, g.stream());
+    if (e) return launch_status(e);
+    if (const int st = g.finish()) return st;
+  }
+  own.x = nullptr;
+  *out = x;
+  return LVA_OK;
+}
+
+// the tables of an index where a mapping call's frame can read them: uploaded with the call, or resident since the build
+struct IndexTables {
+  Piece<uint32_t> offsets;
+  Piece<int32_t> lists;
+  Piece<uint64_t> masks;
+  Piece<int32_t> lens;
+  IndexTables(Frame& f, const lva_map_index* idx, bool with_lens) {
+    const size_t nr = (size_t)idx->n_refs;
+    if (idx->device >= 0) {
+      offsets = f.resident(idx->d_offsets, mi_table(idx->k) + 1);
+      lists = f.resident(idx->d_lists, (size_t)idx->pairs);
+      masks = f.resident(idx->d_masks, mp_mask_words(idx->n_refs, idx->ref_len));
+      if (with_lens) lens = f.resident(idx->d_lens, nr);
+    } else {
+      offsets = f.in(idx->offsets.data(), idx->offsets.size());
+      lists = f.in(idx->lists.data(), idx->lists.size());
+      masks = f.in(idx->masks.data(), idx->masks.size());
+      if (with_lens) lens = f.in(idx->lens.data(), nr);
+    }
+  }
+};
+
 }  // namespace
 
 extern "C" {
+
+int lva_map_index_create_device(int32_t device, const uint8_t* refs, const int64_t* ref_off, int32_t n_refs, int32_t k, int32_t max_occ,
+                                lva_map_index** out) {
+  if (!refs || !ref_off || !out || n_refs < 1 || k < kMpMinK || k > kMpMaxK || max_occ < 1 || max_occ > 65535) return LVA_ERR_ARG;
+  if (index_offsets_args(ref_off, n_refs) != LVA_OK) return LVA_ERR_ARG;
+  return build_map_index_device(device, refs, ref_off, n_refs, k, max_occ, out);
+}
+
+int lva_map_index_tables(const lva_map_index* idx, uint32_t* offsets, int32_t* lists, uint64_t* masks) {
+  if (!idx) return LVA_ERR_ARG;
+  const size_t n_off = mi_table(idx->k) + 1, n_lists = (size_t)idx->pairs, n_masks = mp_mask_words(idx->n_refs, idx->ref_len);
+  if (idx->device < 0) {
+    if (offsets) std::memcpy(offsets, idx->offsets.data(), n_off * sizeof(uint32_t));
+    if (lists && n_lists) std::memcpy(lists, idx->lists.data(), n_lists * sizeof(int32_t));
+    if (masks) std::memcpy(masks, idx->masks.data(), n_masks * sizeof(uint64_t));
+    return LVA_OK;
+  }
+  if (hipSetDevice(idx->device) != hipSuccess) return LVA_ERR_NO_DEVICE;   // the tables' device, like every call that works on one
+  if (offsets) HIP_TRY(hipMemcpy(offsets, idx->d_offsets, n_off * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (lists && n_lists) HIP_TRY(hipMemcpy(lists, idx->d_lists, n_lists * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (masks) HIP_TRY(hipMemcpy(masks, idx->d_masks, n_masks * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return LVA_OK;
+}
 
 int lva_map_index_create(const uint8_t* refs, int32_t n_refs, int32_t ref_len, int32_t k, int32_t max_occ, lva_map_index** out) {
   if (!refs || !out || n_refs < 1 || ref_len < 1 || ref_len > kMaxRef || k < kMpMinK || k > kMpMaxK) return LVA_ERR_ARG;
@@ -1164,10 +1309,7 @@ int lva_map_index_create(const uint8_t* refs, int32_t n_refs, int32_t ref_len, i
 int lva_map_index_create_pooled(const uint8_t* refs, const int64_t* ref_off, int32_t n_refs, int32_t k, int32_t max_occ,
                                 lva_map_index** out) {
   if (!refs || !ref_off || !out || n_refs < 1 || k < kMpMinK || k > kMpMaxK || max_occ < 1 || max_occ > 65535) return LVA_ERR_ARG;
-  size_t total;
-  if (check_offsets(ref_off, n_refs, &total) != LVA_OK) return LVA_ERR_ARG;
-  for (int32_t o = 0; o < n_refs; ++o)
-    if (ref_off[o + 1] - ref_off[o] < 1 || ref_off[o + 1] - ref_off[o] > kMaxRef) return LVA_ERR_ARG;
+  if (index_offsets_args(ref_off, n_refs) != LVA_OK) return LVA_ERR_ARG;
   return build_map_index(refs, ref_off, n_refs, k, max_occ, out);
 }
 
@@ -1185,6 +1327,7 @@ int lva_map_reads(int32_t device, const lva_map_index* idx, const uint8_t* bases
                   int32_t n_reads, int32_t cands, int32_t min_votes, int32_t max_dist, int32_t chunk_reads, int32_t* out) {
   if (map_args(idx, bases, first_base, n_bases, n_reads, cands, min_votes, max_dist, chunk_reads, out) != LVA_OK) return LVA_ERR_ARG;
   if (idx->ragged) return LVA_ERR_ARG;                    // one ref_len for all: lva_map_reads_pooled takes the others
+  if (idx->device >= 0 && idx->device != device) return LVA_ERR_ARG;       // the tables live on another device
   if (n_reads == 0) return LVA_OK;
   const size_t n = (size_t)n_reads;
   Windows w;                                             // (outlives the call's frame)
@@ -1193,18 +1336,16 @@ int lva_map_reads(int32_t device, const lva_map_index* idx, const uint8_t* bases
   w.pack(f, bases, first_base, n_bases, n);              // every read, as given
   size_t chunk = std::min(n, kMpChunkBytes / (kMpMaxCands * sizeof(uint64_t)));
   if (chunk_reads > 0) chunk = std::min(chunk, (size_t)chunk_reads);
-  const auto d_off = f.in(idx->offsets.data(), idx->offsets.size());
-  const auto d_lists = f.in(idx->lists.data(), idx->lists.size());
-  const auto d_masks = f.in(idx->masks.data(), idx->masks.size());
+  const IndexTables t(f, idx, false);
   const auto d_cand = f.scratch<uint64_t>(chunk * kMpMaxCands);
   const auto d_out = f.out(out, 8 * n);
   if (const int st = f.begin()) return st;
   for (size_t a = 0; a < n; a += chunk) {                // a read's row depends on the read alone: chunks change nothing
     const int32_t c = (int32_t)std::min(chunk, n - a);
     const Windows::Chunk x = w.from(a);
-    int e = launch_mp_vote(x.bases, x.off, x.len, c, d_off, d_lists, idx->k, idx->n_refs, min_votes, cands, d_cand, f.stream());
-    if (!e) e = launch_mp_verify(x.bases, x.off, x.len, c, d_cand, d_masks, idx->ref_len, cands, max_dist, d_out.ptr() + 8 * a, f.stream());
-    if (!e) e = launch_mp_start(x.bases, x.off, x.len, c, d_masks, idx->ref_len, d_out.ptr() + 8 * a, f.stream());
+    int e = launch_mp_vote(x.bases, x.off, x.len, c, t.offsets, t.lists, idx->k, idx->n_refs, min_votes, cands, d_cand, f.stream());
+    if (!e) e = launch_mp_verify(x.bases, x.off, x.len, c, d_cand, t.masks, idx->ref_len, cands, max_dist, d_out.ptr() + 8 * a, f.stream());
+    if (!e) e = launch_mp_start(x.bases, x.off, x.len, c, t.masks, idx->ref_len, d_out.ptr() + 8 * a, f.stream());
     if (e) return launch_status(e);
   }
   return f.finish();
@@ -1215,6 +1356,7 @@ int lva_map_reads_pooled(int32_t device, const lva_map_index* idx, const uint8_t
                          int32_t chunk_reads, int32_t* out, int32_t* supp) {
   if (map_pooled_args(idx, bases, first_base, n_bases, n_reads, cands, min_votes, max_dist, min_flank, chunk_reads, out, supp) != LVA_OK)
     return LVA_ERR_ARG;
+  if (idx->device >= 0 && idx->device != device) return LVA_ERR_ARG;       // the tables live on another device
   if (n_reads == 0) return LVA_OK;
   const size_t n = (size_t)n_reads, nr = (size_t)idx->n_refs;
   const bool flanks = min_flank > 0;
@@ -1224,10 +1366,7 @@ int lva_map_reads_pooled(int32_t device, const lva_map_index* idx, const uint8_t
   w.pack(f, bases, first_base, n_bases, n);              // every read, as given
   size_t chunk = std::min(n, kMpChunkBytes / (kMpMaxCands * sizeof(uint64_t)));
   if (chunk_reads > 0) chunk = std::min(chunk, (size_t)chunk_reads);
-  const auto d_off = f.in(idx->offsets.data(), idx->offsets.size());
-  const auto d_lists = f.in(idx->lists.data(), idx->lists.size());
-  const auto d_masks = f.in(idx->masks.data(), idx->masks.size());
-  const auto d_lens = f.in(idx->lens.data(), nr);
+  const IndexTables t(f, idx, true);
   const auto d_max = f.in(max_dist, nr);
   const auto d_cand = f.scratch<uint64_t>(chunk * kMpMaxCands);
   const auto d_out = f.out(out, 8 * n);
@@ -1240,15 +1379,15 @@ int lva_map_reads_pooled(int32_t device, const lva_map_index* idx, const uint8_t
     const int32_t c = (int32_t)std::min(chunk, n - a);
     const Windows::Chunk x = w.from(a);
     int32_t* o = d_out.ptr() + 8 * a;
-    int e = launch_mp_vote(x.bases, x.off, x.len, c, d_off, d_lists, idx->k, idx->n_refs, min_votes, cands, d_cand, f.stream());
-    if (!e) e = launch_mq_verify(x.bases, x.off, x.len, c, d_cand, d_masks, d_lens, idx->ref_len, cands, d_max, o, f.stream());
-    if (!e) e = launch_mq_start(x.bases, x.off, x.len, c, d_masks, d_lens, idx->ref_len, nullptr, o, f.stream());
+    int e = launch_mp_vote(x.bases, x.off, x.len, c, t.offsets, t.lists, idx->k, idx->n_refs, min_votes, cands, d_cand, f.stream());
+    if (!e) e = launch_mq_verify(x.bases, x.off, x.len, c, d_cand, t.masks, t.lens, idx->ref_len, cands, d_max, o, f.stream());
+    if (!e) e = launch_mq_start(x.bases, x.off, x.len, c, t.masks, t.lens, idx->ref_len, nullptr, o, f.stream());
     if (!e && flanks) {
       int32_t* s = d_supp.ptr() + 8 * a;
       e = launch_mq_flank(x.off, x.len, c, o, min_flank, d_foff, d_flen, d_fshift, f.stream());
-      if (!e) e = launch_mp_vote(x.bases, d_foff, d_flen, c, d_off, d_lists, idx->k, idx->n_refs, min_votes, cands, d_cand, f.stream());
-      if (!e) e = launch_mq_verify(x.bases, d_foff, d_flen, c, d_cand, d_masks, d_lens, idx->ref_len, cands, d_max, s, f.stream());
-      if (!e) e = launch_mq_start(x.bases, d_foff, d_flen, c, d_masks, d_lens, idx->ref_len, d_fshift, s, f.stream());
+      if (!e) e = launch_mp_vote(x.bases, d_foff, d_flen, c, t.offsets, t.lists, idx->k, idx->n_refs, min_votes, cands, d_cand, f.stream());
+      if (!e) e = launch_mq_verify(x.bases, d_foff, d_flen, c, d_cand, t.masks, t.lens, idx->ref_len, cands, d_max, s, f.stream());
+      if (!e) e = launch_mq_start(x.bases, d_foff, d_flen, c, t.masks, t.lens, idx->ref_len, d_fshift, s, f.stream());
     }
     if (e) return launch_status(e);
   }

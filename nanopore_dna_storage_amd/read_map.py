@@ -57,7 +57,14 @@ pass" of the following, and every call of that case returns the same integers as
 On the device a ragged index, a max_dist array or min_flank > 0 goes through lva_map_reads_pooled (csrc/mq_kernels.hip), held
 to this definition bit for bit, out and supp (tests/test_gpu_read_map_pooled.py); everything else through lva_map_reads.
 
-Out of scope: an index built on the device."""
+The index on the device.  MapIndex(..., device=d) uploads the oligos and builds the index there (lva_map_index_create_device,
+csrc/mi_kernels.hip): the match masks; a histogram of 4^k counters in which every oligo counts each of its distinct k-mers
+once; the counters above max_occ cleared; an exclusive prefix sum in three launches (a sum per tile, a scan of the sums, an
+add) for the offsets; every kept pair placed in its k-mer's segment by an atomic, then moved to its rank among the segment's
+oligos, so that a list is ascending whatever order the atomics ran in.  The tables are the bytes the host builder makes
+(MapIndex.tables(), tests/test_gpu_map_index.py) and stay on the device until the index is closed: map_reads with such an
+index uploads the reads alone and returns the same integers.  The command line takes --index device.  Out of scope:
+error_profile --assign map and pooled --assign map keep the host index, and basecalls still pass through the host."""
 import argparse
 import ctypes
 import sys
@@ -318,21 +325,27 @@ def reference_map(bases, windows, refs, k=10, max_occ=64, cands=4, min_votes=2, 
 
 
 class MapIndex:
-    """The index of a set of oligos (lva_map_index_create, lva_map_index_create_pooled where their lengths differ: the k-mer
-    table and the oligos' match masks, built on the host); owns the handle, a context manager.  refs: what the module's
-    docstring lists; groups: optional int32 [n_refs], carried into the results of map_reads.  refs is the rectangular array
-    where the lengths are equal, else None; lens [n_refs]; ref_len is the longest."""
+    """The index of a set of oligos: the k-mer table and the oligos' match masks; owns the handle, a context manager.
+    device None: built on the host (lva_map_index_create, lva_map_index_create_pooled where the lengths differ), every
+    map_reads call uploads it; an ordinal: built on that device from the uploaded oligos (lva_map_index_create_device) and
+    resident there until close(), the same tables, and map_reads uploads the reads alone.  refs: what the module's docstring
+    lists; groups: optional int32 [n_refs], carried into the results of map_reads.  refs is the rectangular array where the
+    lengths are equal, else None; lens [n_refs]; ref_len is the longest."""
 
-    def __init__(self, refs, k=10, max_occ=64, groups=None):
+    def __init__(self, refs, k=10, max_occ=64, groups=None, device=None):
         self._h = None
         self.oligos = Oligos(refs)
         self.refs, self.lens = self.oligos.refs, self.oligos.lens
         self.groups = _groups(groups, len(self.lens))
         self.k, self.max_occ = int(k), int(max_occ)
+        self.device = None if device is None else int(device)
         _parameters(self.lens, self.k, self.max_occ, 1, 1, 0)
         self._L = load_library()
         h = ctypes.c_void_p()
-        if self.ragged:
+        if self.device is not None:
+            check(self._L.lva_map_index_create_device(self.device, self.oligos.flat.ctypes.data, self.oligos.off.ctypes.data, self.n_refs,
+                                                      self.k, self.max_occ, ctypes.byref(h)))
+        elif self.ragged:
             check(self._L.lva_map_index_create_pooled(self.oligos.flat.ctypes.data, self.oligos.off.ctypes.data, self.n_refs, self.k,
                                                       self.max_occ, ctypes.byref(h)), None)
         else:
@@ -355,6 +368,14 @@ class MapIndex:
         check(self._L.lva_map_index_info(self.handle, *(ctypes.addressof(got) + 8 * i for i in range(3))), None)
         return tuple(int(x) for x in got)
 
+    def tables(self):
+        """(offsets uint32 [4^k + 1], lists int32 [pairs], masks uint64 [n_refs, 2, 4, ceil(ref_len / 64)]) copied to the host:
+        the oligos of k-mer c are lists[offsets[c]:offsets[c + 1]], ascending; the same bytes however the index was built"""
+        offsets, lists = np.zeros(4 ** self.k + 1, np.uint32), np.zeros(self.info()[1], np.int32)
+        masks = np.zeros((self.n_refs, 2, 4, (self.ref_len + 63) // 64), np.uint64)
+        check(self._L.lva_map_index_tables(self.handle, offsets.ctypes.data, lists.ctypes.data, masks.ctypes.data))
+        return offsets, lists, masks
+
     def close(self):
         if self._h is not None:
             self._L.lva_map_index_destroy(self._h)
@@ -373,8 +394,11 @@ class MapIndex:
 def map_reads(bases, windows, index, cands=4, min_votes=2, max_dist=None, device=0, chunk_reads=0, min_flank=0):
     """reference_map on the device, all reads in one call: the same integers.  index: a MapIndex (its k, max_occ and groups);
     chunk_reads: reads per pass over the device buffers, 0 = as many as fit; the result does not depend on it.  A ragged
-    index, a max_dist array or min_flank > 0 goes through lva_map_reads_pooled, everything else through lva_map_reads."""
+    index, a max_dist array or min_flank > 0 goes through lva_map_reads_pooled, everything else through lva_map_reads.  An
+    index built on a device serves the calls on that device: another one is a ValueError."""
     bases, windows = _inputs(bases, windows)
+    if index.device is not None and index.device != device:
+        raise ValueError("the index lives on device %d, the call is for device %d" % (index.device, device))
     pooled = index.ragged or min_flank > 0 or not (max_dist is None or np.ndim(max_dist) == 0)
     max_dist = np.minimum(_parameters(index.lens, index.k, index.max_occ, cands, min_votes, max_dist, min_flank), 2 ** 31 - 1).astype(np.int32)
     if not len(bases):
@@ -412,6 +436,9 @@ def build_parser():
                         "the shortest oligo (the default with several oligo files; with one file the default is no pass)")
     p.add_argument("--chunk", type=int, default=4096, help="reads per pass over the manifest")
     p.add_argument("--device", type=int, default=0)
+    p.add_argument("--index", choices=("host", "device"), default="host",
+                   help="where the index is built: on the host, uploaded with every chunk, or on --device, resident there for "
+                        "the run; the files are the same")
     return p
 
 
@@ -449,7 +476,7 @@ def main(argv=None, out=sys.stdout, decoder=None):
     dec = Decoder(6, 1, 60, list_size=1, max_deviation=20, device=a.device) if own else decoder
     parts, supps = [], []
     try:
-        with MapIndex(oligos, a.k, a.max_occ, groups if pooled else None) as index:
+        with MapIndex(oligos, a.k, a.max_occ, groups if pooled else None, device=a.device if a.index == "device" else None) as index:
             for at in range(0, len(rows), max(1, a.chunk)):
                 with dec.resident([helper.read_post_file(row[2]) for row in rows[at:at + max(1, a.chunk)]]) as (dev, off):
                     calls = [b for b, _ in dec.basecall_resident(dev, off)]
