@@ -109,7 +109,7 @@ const char *lva_version(void);
 /* LVA_ABI_VERSION of the library that was loaded.  It changes whenever a struct of this header changes size or layout
  * (5: lva_profile gained overflow_steps and working_bytes): a caller built against another value must not pass structs.
  * Entry points added since (lva_stream_*, lva_transpost_*, lva_device_download, lva_list_*, lva_demux_*, lva_kernel_plan,
- * lva_align_profile, lva_map_index_*, lva_map_reads, lva_map_reads_pooled) change no struct and keep it at 5. */
+ * lva_align_profile, lva_map_index_*, lva_map_reads, lva_map_reads_pooled, lva_score_bases*) change no struct and keep it at 5. */
 #define LVA_ABI_VERSION 5
 int lva_abi_version(void);
 const char *lva_strerror(int code);
@@ -592,6 +592,39 @@ int lva_align_profile(int32_t device, const uint8_t *bases, const int64_t *first
                       const uint8_t *refs, int32_t n_refs, int32_t ref_len, const int32_t *ref_id,
                       const uint8_t *rc /* NULL: none */, int32_t chunk_reads /* 0: as many as fit 1 GiB */, int32_t *out_read,
                       int64_t *out_pos, int64_t *out_conf, int64_t *out_ins);
+
+/* --- what a GIVEN base sequence scores on a read ---------------------
+ * The reference trellis (decode_post_conv_parallel_LVA, :589-858) restricted to one message: a path that carries message M
+ * walks M's convolutional states, so what is left is a band of positions x flip-flop states per block -- a forced alignment
+ * of the read's posteriors to M's base sequence under the decoder's band, with the reference's two parity buffers that are
+ * never cleared.  Every score of a decoded list is one of the two values returned for the listed message, bit for bit.  The
+ * definition is nanopore_dna_storage_amd/trellis_score.py (reference_score; message_bases gives the sequence of a message
+ * under either rc flag); the kernel is csrc/sc_kernels.hip.
+ *   post_dev     a resident posterior buffer (lva_device_upload, lva_transpost_batch_device, the simulator), read i = the
+ *                n_blocks[i] blocks from block first_block[i] on, as lva_decode_windows_device takes them;
+ *   bases        sequence s = bases[first_base[s] .. + n_bases[s]), codes 0..3 or the characters ACGT, 1 .. 1024 bases each
+ *                (the windows of lva_align_profile); the decoder's code does not constrain them: a sequence of n bases has
+ *                n + 1 positions, and the band of a pair is lva_band_table's formula for (n_blocks, n + 1, max_deviation);
+ *   pairs        int32 [n_pairs][2] = (read, sequence), any order, any number per read;
+ *   max_deviation  LVA_MAX_DEVIATION_DEFAULT: the decoder's own; msg_len + mem_conv + 1 or more switches the band off;
+ *   out          float [n_pairs][2] = (flip, flop): the scores of the two states of the last base at the last position.
+ * Refusals, nothing is launched or allocated: LVA_ERR_ARG for a pair index out of range, a sequence that is empty or longer
+ * than 1024, a base that is neither a code 0..3 nor ACGT, a window (paired or not) that is negative, has more than 2^20
+ * blocks (the limit of every stage, above) or ends at or beyond block 2^31, and a call whose band tables -- one of n_blocks
+ * words per distinct (n_blocks, sequence length) among the pairs -- pass 2^26 words;
+ * LVA_ERR_POST_TOO_SHORT for a pair whose window has fewer than n + 2 blocks (the reference's "Too small post matrix");
+ * LVA_ERR_BUSY while a decode stream is open.  n_pairs = 0 succeeds and touches nothing.  Posteriors are finite or -inf
+ * (NaN and +inf are outside the definition; the device does not look for them and what it returns for such a read is not
+ * specified).  The calls run on the decoder's stream, are complete on return and leave
+ * the decoder's profile alone.  lva_score_bases takes host posteriors with row_offsets as lva_decode_batch does, uploads
+ * them and does the same. */
+int lva_score_bases_device(lva_decoder *d, const float *post_dev, const int64_t *first_block, const int64_t *n_blocks,
+                           int32_t n_reads, const uint8_t *bases, const int64_t *first_base, const int32_t *n_bases,
+                           int32_t n_seqs, const int32_t *pairs, int32_t n_pairs, uint32_t max_deviation, float *out);
+int lva_score_bases(lva_decoder *d, const float *post, const int64_t *row_offsets, int32_t n_reads, const uint8_t *bases,
+                    const int64_t *first_base, const int32_t *n_bases, int32_t n_seqs, const int32_t *pairs, int32_t n_pairs,
+                    uint32_t max_deviation, float *out);
+
 
 /* ---------------------------------------------------------------------------------------------
  * reads mapped to oligos -- for reads that carry no index of their own (a list that failed the

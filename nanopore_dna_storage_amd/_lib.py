@@ -145,6 +145,8 @@ ABI = {
     "lva_simulate_pool_plan": (_int, _sim + _pool + [_vp, _vp]),
     "lva_simulate_pool_fill_device": (_int, _sim + _pool + [_f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lva_align_profile": (_int, [_i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "lva_score_bases_device": (_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _u32, _vp]),
+    "lva_score_bases": (_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _u32, _vp]),
     "lva_map_index_create_device": (_int, [_i32, _vp, _vp, _i32, _i32, _i32, ctypes.POINTER(_vp)]),
     "lva_map_index_tables": (_int, [_vp, _vp, _vp, _vp]),
     "lva_map_index_create_pooled": (_int, [_vp, _vp, _i32, _i32, _i32, ctypes.POINTER(_vp)]),

@@ -229,7 +229,9 @@ int Code::fingerprint(const uint8_t* msg, uint32_t n_bits, uint32_t* out) const 
   return LVA_OK;
 }
 
-void Code::band(uint32_t t, uint32_t nblk, uint32_t max_dev, uint32_t* lo, uint32_t* hi) const {
+void Code::band(uint32_t t, uint32_t nblk, uint32_t max_dev, uint32_t* lo, uint32_t* hi) const { band_of(npos, t, nblk, max_dev, lo, hi); }
+
+void band_of(uint32_t npos, uint32_t t, uint32_t nblk, uint32_t max_dev, uint32_t* lo, uint32_t* hi) {
   // :677-679.  `(double)t / nblk * nstate_pos - max_deviation` is contracted to one fused
   // multiply-subtract by g++ -O3 -march=native (install.sh:9) on FMA hosts, and the reference
   // results depend on it (about 1 step in 1400 lands on a different integer otherwise).

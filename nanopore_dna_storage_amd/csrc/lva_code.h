@@ -68,6 +68,10 @@ struct Code {
   void working_band(uint32_t t, uint32_t nblk, uint32_t max_dev, uint32_t* lo, uint32_t* hi) const;
 };
 
+// THE band formula (:677-679) for a trellis of npos positions: Code::band is this with the code's npos, the one-message
+// trellis (lva_score_bases) takes it with the positions of a base sequence
+void band_of(uint32_t npos, uint32_t t, uint32_t nblk, uint32_t max_dev, uint32_t* lo, uint32_t* hi);
+
 // set_conv_params (:264-415).  Returns 0 or a negative LVA_ERR_* code (include/lva_decoder.h).
 int build_code(Code* c, int mem_conv, int rate, uint32_t msg_len, int rc, const char* sync_marker,
                uint32_t sync_period);

@@ -1,11 +1,12 @@
 // lva_stages.cpp -- C ABI (include/lva_decoder.h) of the stages beside the list decoder: transition posteriors (N0), basecall
 // and barcode localisation (N3), demultiplexing (N3'), the consumers of a decoded list (N2), the Reed-Solomon outer code (N4),
-// reading-cost trials (N4'), the read simulator (S), the error profile (N5), read mapping (N6).  No algorithm lives here: an entry point checks its arguments, then works
+// reading-cost trials (N4'), the read simulator (S), the error profile (N5), read mapping (N6), the one-message trellis (N7).  No algorithm lives here: an entry point checks its arguments, then works
 // through one Frame (below): it declares its device pieces together with their host side, begins (allocate, upload),
 // launches, finishes (copy back, wait).
 #include <algorithm>
 #include <cstring>
 #include <new>
+#include <utility>
 
 #include "lva_host.h"
 #include "bc_kernels.h"
@@ -18,6 +19,7 @@
 #include "mp_kernels.h"
 #include "mq_kernels.h"
 #include "mi_kernels.h"
+#include "sc_kernels.h"
 
 using namespace lva;
 
@@ -1392,6 +1394,118 @@ int lva_map_reads_pooled(int32_t device, const lva_map_index* idx, const uint8_t
     if (e) return launch_status(e);
   }
   return f.finish();
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// what a given base sequence scores on a read -- the reference trellis restricted to one
+// message (csrc/sc_kernels.hip; the definition is trellis_score.py).  Bound to a decoder: its stream, its max_deviation
+// by default, posteriors where the decode calls read them.  The code's npos does not constrain a sequence; the band of a
+// pair is the band formula's for (the read's blocks, the sequence's positions), evaluated on the host as the decode
+// path evaluates its own (band_of, lva_code.cpp) and shared by the pairs that agree in both.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// Band words of one call at most (256 MiB on the host and on the device): one table per distinct (blocks, positions) among
+// the pairs.  A run of 2 000 reads scored against its own lists needs 2 M words; 2^26 is 64 reads of 2^20 blocks each.
+constexpr size_t kScMaxBandWords = (size_t)1 << 26;
+
+// everything that can be refused without the device, in the order of include/lva_decoder.h
+int score_args(const int64_t* first_block, const int64_t* n_blocks, int32_t n_reads, const uint8_t* bases, const int64_t* first_base,
+               const int32_t* n_bases, int32_t n_seqs, const int32_t* pairs, int32_t n_pairs, const float* post, const float* out) {
+  if (n_reads < 0 || n_seqs < 0 || n_pairs < 0) return LVA_ERR_ARG;
+  if (n_reads > 0 && (!post || !first_block || !n_blocks)) return LVA_ERR_ARG;
+  if (n_seqs > 0 && (!bases || !first_base || !n_bases)) return LVA_ERR_ARG;
+  if (n_pairs > 0 && (!pairs || !out)) return LVA_ERR_ARG;
+  for (int32_t i = 0; i < n_reads; ++i)                  // 32-bit block offsets inside the kernel, as everywhere
+    if (first_block[i] < 0 || n_blocks[i] < 0 || n_blocks[i] > kBcMaxBlocks || first_block[i] + n_blocks[i] >= ((int64_t)1 << 31))
+      return LVA_ERR_ARG;
+  if (Windows::check(first_base, n_bases, n_seqs, kMaxRef) != LVA_OK) return LVA_ERR_ARG;        // a sequence longer than kMaxRef
+  for (int32_t s = 0; s < n_seqs; ++s) {
+    if (n_bases[s] < 1) return LVA_ERR_ARG;
+    for (int32_t j = 0; j < n_bases[s]; ++j)
+      if (base_code(bases[first_base[s] + j]) >= kBaseN) return LVA_ERR_ARG;                      // a base code above 3
+  }
+  for (int32_t k = 0; k < n_pairs; ++k)
+    if (pairs[2 * k] < 0 || pairs[2 * k] >= n_reads || pairs[2 * k + 1] < 0 || pairs[2 * k + 1] >= n_seqs) return LVA_ERR_ARG;
+  for (int32_t k = 0; k < n_pairs; ++k)                  // nblk < npos + 1: "Too small post matrix" (:600-601)
+    if (n_blocks[pairs[2 * k]] < (int64_t)n_bases[pairs[2 * k + 1]] + 2) return LVA_ERR_POST_TOO_SHORT;
+  return LVA_OK;
+}
+
+// lva_score_bases (post on the host, read i = blocks [first_block[i], + n_blocks[i]) of it, T blocks in all: uploaded) and
+// lva_score_bases_device (post the caller's device buffer)
+int score_stage(lva_decoder* d, const float* post, size_t host_blocks, bool post_on_host, const int64_t* first_block,
+                const int64_t* n_blocks, int32_t n_reads, const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases,
+                int32_t n_seqs, const int32_t* pairs, int32_t n_pairs, uint32_t max_deviation, float* out) {
+  if (!d) return LVA_ERR_ARG;
+  int st = score_args(first_block, n_blocks, n_reads, bases, first_base, n_bases, n_seqs, pairs, n_pairs, post, out);
+  if (st != LVA_OK) return st;
+  st = stage_enter(d, n_pairs == 0);
+  if (st != kRun) return st;
+  const uint32_t max_dev = max_deviation == LVA_MAX_DEVIATION_DEFAULT ? d->max_dev : max_deviation;
+  // the pairs as the kernel reads them; one band table per (blocks, positions) that occurs
+  Windows w;                                             // (these outlive the call's frame)
+  std::vector<ScPair> sp((size_t)n_pairs);
+  std::vector<uint32_t> band;
+  std::vector<std::pair<uint64_t, uint32_t>> keys((size_t)n_pairs);          // (blocks << 32 | positions, pair)
+  int32_t max_len = 1;
+  for (int32_t k = 0; k < n_pairs; ++k) {
+    const int32_t r = pairs[2 * k], s = pairs[2 * k + 1];
+    keys[k] = {(uint64_t)n_blocks[r] << 32 | (uint32_t)(n_bases[s] + 1), (uint32_t)k};
+    max_len = std::max(max_len, n_bases[s]);
+  }
+  std::sort(keys.begin(), keys.end());
+  size_t band_words = 0;                                 // refused before anything is allocated: kScMaxBandWords
+  for (size_t i = 0; i < keys.size(); ++i)
+    if (i == 0 || keys[i].first != keys[i - 1].first) band_words += (size_t)(keys[i].first >> 32);
+  if (band_words > kScMaxBandWords) return LVA_ERR_ARG;
+  band.reserve(band_words);
+  Frame f(d->stream);
+  w.pack(f, bases, first_base, n_bases, (size_t)n_seqs);
+  for (size_t i = 0; i < keys.size(); ++i) {
+    const uint32_t k = keys[i].second, nblk = (uint32_t)(keys[i].first >> 32), npos = (uint32_t)keys[i].first;
+    if (i == 0 || keys[i].first != keys[i - 1].first)
+      for (uint32_t t = 0; t < nblk; ++t) {
+        uint32_t lo, hi;
+        band_of(npos, t, nblk, max_dev, &lo, &hi);
+        band.push_back(lo | hi << 16);                   // hi <= npos <= kMaxRef + 1
+      }
+    sp[k] = ScPair{(uint32_t)first_block[pairs[2 * k]], nblk, (uint32_t)w.win_off[(size_t)pairs[2 * k + 1]], npos - 1,
+                   (uint32_t)(band.size() - nblk)};
+  }
+  const Piece<float> up = post_on_host ? f.in(post, kPostRow * host_blocks) : Piece<float>{};
+  const auto d_pairs = f.in(sp.data(), sp.size());
+  const auto d_band = f.in(band.data(), band.size());
+  const auto d_out = f.out(out, 2 * (size_t)n_pairs);
+  if ((st = f.begin()) != LVA_OK) return st;
+  const int e = launch_sc_score(post_on_host ? up.ptr() : post, w.bases, d_pairs, d_band, n_pairs, max_len, d_out, f.stream());
+  if (e) return launch_status(e);
+  return f.finish();
+}
+
+}  // namespace
+
+extern "C" {
+
+int lva_score_bases_device(lva_decoder* d, const float* post_dev, const int64_t* first_block, const int64_t* n_blocks, int32_t n_reads,
+                           const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases, int32_t n_seqs,
+                           const int32_t* pairs, int32_t n_pairs, uint32_t max_deviation, float* out) {
+  return score_stage(d, post_dev, 0, false, first_block, n_blocks, n_reads, bases, first_base, n_bases, n_seqs, pairs, n_pairs,
+                     max_deviation, out);
+}
+
+int lva_score_bases(lva_decoder* d, const float* post, const int64_t* row_offsets, int32_t n_reads, const uint8_t* bases,
+                    const int64_t* first_base, const int32_t* n_bases, int32_t n_seqs, const int32_t* pairs, int32_t n_pairs,
+                    uint32_t max_deviation, float* out) {
+  if (!d || n_reads < 0 || !row_offsets) return LVA_ERR_ARG;
+  size_t T = 0;
+  if (check_offsets(row_offsets, n_reads, &T) != LVA_OK) return LVA_ERR_ARG;
+  const std::vector<int32_t> len = read_lengths(row_offsets, n_reads);
+  const std::vector<int64_t> nb(len.begin(), len.end());
+  return score_stage(d, post, T, true, row_offsets, nb.data(), n_reads, bases, first_base, n_bases, n_seqs, pairs, n_pairs,
+                     max_deviation, out);
 }
 
 }  // extern "C"

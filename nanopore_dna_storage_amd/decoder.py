@@ -160,6 +160,7 @@ class Decoder:
         self._h = h
         self.mem_conv, self.rate, self.msg_len, self.list_size = mem_conv, rate, msg_len, list_size
         self.device = device
+        self._sync_period = sync_period
 
     def close(self):
         if getattr(self, "_h", None):
@@ -287,6 +288,65 @@ class Decoder:
             for i, r in zip(good, dec):
                 out[i] = (loc[i], r)
         return out
+
+    # --- what a given sequence or message scores on a read (trellis_score.py is the definition) -----
+    def _score(self, fn, where, n_reads, seqs, pairs, max_deviation):
+        """the one score call: `where` is what the entry point takes between the decoder and n_reads"""
+        from .trellis_score import as_codes
+        seqs = [as_codes(s) for s in seqs]
+        lens = np.array([len(s) for s in seqs], dtype=np.int32)
+        first = np.zeros(len(seqs), np.int64)
+        first[1:] = np.cumsum(lens[:-1], dtype=np.int64)
+        bases = np.concatenate(seqs + [np.zeros(1, np.uint8)])
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        out = np.zeros((len(pr), 2), np.float32)
+        md = _lib.MAX_DEVIATION_DEFAULT if max_deviation is None else int(max_deviation)
+        self._check(fn(self._h, *where, n_reads, bases.ctypes.data, first.ctypes.data, lens.ctypes.data, len(seqs), pr.ctypes.data,
+                       len(pr), md, out.ctypes.data))
+        return out
+
+    def score_bases(self, posts, seqs, pairs, max_deviation=None):
+        """The reference trellis restricted to one base sequence, per (read, sequence) pair: posts as decode() takes them,
+        seqs a list of base sequences (codes 0..3 or ACGT; any lengths from 1 to 1024, the code does not constrain them),
+        pairs [(read, sequence)] in any order, max_deviation None: the decoder's.  -> float32 [n_pairs, 2] = (flip, flop),
+        bit for bit trellis_score.reference_score(posts[r], seqs[s], max_deviation).  Raises LvaError for an index out of
+        range and for a read shorter than its sequence's positions + 1 (LVA_ERR_POST_TOO_SHORT)."""
+        flat, off = self._pack(posts)
+        return self._score(self._L.lva_score_bases, (flat.ctypes.data, off.ctypes.data), len(off) - 1, seqs, pairs, max_deviation)
+
+    def score_bases_resident(self, dev_ptr, first_block, n_blocks, seqs, pairs, max_deviation=None):
+        """score_bases() on windows [first_block[i], first_block[i] + n_blocks[i]) of a resident posterior buffer, as
+        decode_windows_resident reads them: a decode and the scores of its entries read the same memory"""
+        fb = np.ascontiguousarray(first_block, dtype=np.int64)
+        nb = np.ascontiguousarray(n_blocks, dtype=np.int64)
+        return self._score(self._L.lva_score_bases_device, (dev_ptr, fb.ctypes.data, nb.ctypes.data), len(fb), seqs, pairs,
+                           max_deviation)
+
+    def score_messages(self, posts, msgs, pairs, rc=None):
+        """What messages score on reads under this decoder's code and max_deviation: msgs uint8 [n_msgs, msg_len] in
+        encode()'s bit order (rows of a decoded list as they are), pairs [(read, message)], rc an optional bool per READ (the
+        flag its decode takes; a message is encoded for the orientation of every read it is paired with).
+        -> float32 [n_pairs, 2]; every score of decode()'s list for a read is one of the two values of its message."""
+        from .trellis_score import message_bases
+        msgs = np.ascontiguousarray(msgs, dtype=np.uint8).reshape(-1, self.msg_len)
+        pr = np.array(pairs, dtype=np.int32).reshape(-1, 2)          # a copy: the message indices become sequence indices below
+        sync = self._sync.decode() if self._sync else ""
+        if len(pr) and (pr[:, 1].min() < 0 or pr[:, 1].max() >= len(msgs)):
+            raise LvaError(-10, "a pair names a message that is not there")
+        flip = np.zeros(len(pr), bool)
+        if rc is not None and len(posts):
+            if len(rc) != len(posts):
+                raise ValueError("rc: one flag per read")
+            flip = np.asarray(rc, dtype=bool)[np.clip(pr[:, 0], 0, len(posts) - 1)]       # (an index out of range: the call refuses it)
+        seqs = []
+        for want in (False, True):                       # forward sequences first, then the reverse complements that are asked for
+            use = np.unique(pr[flip == want, 1])
+            if len(use):
+                enc = message_bases(self.mem_conv, self.rate, self.msg_len, msgs[use], want, sync, self._sync_period)
+                at = dict(zip(use.tolist(), range(len(seqs), len(seqs) + len(use))))
+                seqs += list(enc)
+                pr[flip == want, 1] = [at[m] for m in pr[flip == want, 1].tolist()]
+        return self.score_bases(posts, seqs, pr)
 
     # --- SURVEY 8(f) row N3: basecall of the posterior matrix + barcode localisation ------------
     def _basecall(self, fn, src, off):
@@ -494,18 +554,23 @@ class Decoder:
             yield dev, row, dict(msgs=msgs, bases=bases[:int(base[-1])], base_offsets=base, true_idx=true_idx[:int(row[-1])],
                                  **more)
 
-    def simulate_and_decode(self, n, seed, first_read=0, pool=None, pool_cdf=None, **kw):
+    def simulate_and_decode(self, n, seed, first_read=0, pool=None, pool_cdf=None, after=None, **kw):
         """simulate -> posteriors in place -> decode (with both barcodes: locate_payload_resident -> decode_located) without
         the scores leaving the device -> (truth, results); results as decode() / decode_with_barcodes() give them.  Without
         barcodes the orientation of every read is passed to the decoder as the simulator chose it (rc_mode; with a pool,
-        truth's rc, as drawn)."""
+        truth's rc, as drawn).  after (without barcodes): a function (dev_ptr, row_offsets, truth, results, rc) that is called
+        while the posteriors are still resident -- what it returns is returned third (trellis_score.simulate_rows scores the
+        truth there)."""
         with self.simulate(n, seed, first_read, pool=pool, pool_cdf=pool_cdf, **kw) as (dev, off, truth):
             self.posteriors_resident(dev, off)
             if kw.get("start_barcode") is not None:
+                if after is not None:
+                    raise ValueError("after: reads without barcodes")
                 return truth, self._decode_chain_resident(dev, off, None, kw["start_barcode"], kw["end_barcode"])
             mode = kw.get("rc_mode", 0)
             rc = [mode == 1 or (mode == 2 and bool((first_read + i) & 1)) for i in range(n)] if pool is None else truth["rc"]
-            return truth, self.decode_resident(dev, off, rc)
+            results = self.decode_resident(dev, off, rc)
+            return (truth, results) if after is None else (truth, results, after(dev, off, truth, results, rc))
 
     # --- decode stream: reads go in one at a time, results come out as they finish -------------
     def stream(self, queue_cap=None):

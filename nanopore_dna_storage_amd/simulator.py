@@ -39,6 +39,9 @@ def build_parser():
                         "(Decoder.simulate: the reference's insertion / deletion / substitution rules, transition scores)")
     p.add_argument("--stats", choices=["host", "device"], default="host",
                    help="where the per-trial statistics are computed: Python loops, or the GPU (list_ops.list_stats); same output")
+    p.add_argument("--truth_score", action="store_true",
+                   help="score every trial's true message on the decoder's trellis (trellis_score.py) and add to the summary, "
+                        "per verdict, why a list missed it: the list was too short, or the band cut its path")
     return p
 
 
@@ -53,23 +56,40 @@ def run(args, out=sys.stdout, decoder=None):
     if own:
         decoder = Decoder(args.mem_conv, args.rate, args.msg_len, list_size=args.list_size,
                           max_deviation=args.max_deviation, device=args.device)
+    rows = None
     try:
-        if on_device:      # reads made, turned into posteriors and decoded on the device: the truth is all that comes back
+        if on_device and getattr(args, "truth_score", False):      # the same chain, the truth scored on the buffer the decode read
+            from . import trellis_score
+            truth, results, rows = trellis_score.simulate_rows(decoder, args.num_trials, args.seed, margin=args.margin,
+                                                               sub=args.syn_sub_prob, dele=args.syn_del_prob, ins=args.syn_ins_prob,
+                                                               rc_mode=int(revcomp))
+            oligos = encode(args.mem_conv, args.rate, args.msg_len, truth["msgs"]) if args.num_trials else []
+            reads = [dict(msg=m, oligo=o) for m, o in zip(truth["msgs"], oligos)]
+        elif on_device:      # reads made, turned into posteriors and decoded on the device: the truth is all that comes back
             truth, results = decoder.simulate_and_decode(args.num_trials, args.seed, margin=args.margin, sub=args.syn_sub_prob,
                                                          dele=args.syn_del_prob, ins=args.syn_ins_prob, rc_mode=int(revcomp))
             oligos = encode(args.mem_conv, args.rate, args.msg_len, truth["msgs"]) if args.num_trials else []
             reads = [dict(msg=m, oligo=o) for m, o in zip(truth["msgs"], oligos)]
         else:
-            results = decoder.decode([r["post"] for r in reads], rc=[revcomp] * len(reads))
+            if getattr(args, "truth_score", False):
+                from . import trellis_score
+                with decoder.resident([r["post"] for r in reads]) as (dev, off):
+                    results = decoder.decode_resident(dev, off, [revcomp] * len(reads))
+                    rows = trellis_score.truth_rows(decoder, dev, off[:-1], np.diff(off), results,
+                                                    np.array([r["msg"] for r in reads], dtype=np.uint8).reshape(len(reads), -1),
+                                                    [revcomp] * len(reads))
+            else:
+                results = decoder.decode([r["post"] for r in reads], rc=[revcomp] * len(reads))
     finally:
         if own:
             decoder.close()
-    return report(args, reads, results, out)
+    return report(args, reads, results, out, truth_rows=rows)
 
 
-def report(args, reads, results, out=sys.stdout):
+def report(args, reads, results, out=sys.stdout, truth_rows=None):
     """The per-trial and summary statistics (simulator.py:92-126) of decoded reads: reads = dicts with msg and oligo, results
-    = what Decoder.decode returns for them.  Prints the reference's text to `out` -> the summary statistics."""
+    = what Decoder.decode returns for them.  Prints the reference's text to `out` -> the summary statistics.  truth_rows
+    (--truth_score: trellis_score.truth_rows of the same reads): the count per verdict joins the summary."""
     top, lst, ham, ham8, ham16, edit = [], [], [], [], [], []
     n = args.msg_len
     dev = None
@@ -122,6 +142,10 @@ def report(args, reads, results, out=sys.stdout):
         "Average 16 block error rate of top": sum(ham16) / (math.ceil(n / 16) * T) if T else 0.0,
         "Average edit distance rate of top": sum(edit) / (n * T) if T else 0.0,
     }
+    if truth_rows is not None:
+        from . import trellis_score
+        for verdict, count in trellis_score.count_verdicts(truth_rows).items():
+            stats["Number truth " + verdict] = count
     print("Summary statistics:", file=out)
     for k, v in stats.items():
         print(k + ":", v, file=out)

@@ -1,0 +1,266 @@
+"""What a GIVEN message scores on a read: the reference trellis restricted to one message.
+
+The decoder answers "which list_size messages score best on this read".  This stage answers the question that follows:
+"what would this message have scored?" -- for a read whose list misses the truth it tells a list that was too short from a
+band (max_deviation) that cut the truth's path off.
+
+A path of decode_post_conv_parallel_LVA (viterbi_convolutional_code.cpp:589-858) that carries message M walks M's
+convolutional states, so of the trellis only (position, flip-flop state) is left, and of the eight flip-flop states of a
+position only two can be reached: flip b and flop b + 4 with b the base that M's oligo has there.  What remains is a chain of
+single float32 additions and maxima over a band of positions -- a forced alignment of the read's posteriors to M's base
+sequence under the decoder's band, the decoder's two parity buffers that are never cleared included (a position outside a
+block's band keeps what it held two blocks earlier, and the reference reads it again when the band returns: the "stale band"
+lists of tests/golden/m8_r3_L8_edge*).  Every score of a decoded list is one of the two values this returns for the listed
+message, bit for bit (tests/test_trellis_score_host.py holds reference_score to the oracle on that).
+
+  reference_score   the definition, plain numpy (this file is to csrc/sc_kernels.hip what read_map.py is to mp_kernels.hip);
+  message_bases     the base sequence that a decode with a given rc flag walks for a message;
+  Decoder.score_bases / score_bases_resident / score_messages (decoder.py)   the same on the device, bit for bit;
+  verdicts, main    the use: why did the list of a read miss the truth?
+
+    python -m nanopore_dna_storage_amd.trellis_score --simulate 2000 --seed 1 --mem_conv 11 --rate 5 --msg_len 180 \
+        --list_size 8 --max_deviation 20 --out run        # -> run.truth.tsv and a summary line
+"""
+import argparse
+import sys
+from fractions import Fraction
+
+import numpy as np
+
+from . import decoder as _dec
+
+VERDICTS = ("in_list", "list_too_short", "band", "short_read")      # the tool's, in the order of its summary line
+NEG = np.float32(-np.inf)
+
+
+def _band(t, nblk, npos, max_deviation):
+    """[lo, hi) of block t (:677-679), as lva_band_table gives it for a code of npos positions: the centre is ONE fused
+    multiply-subtract in double (the reference's build contracts it), truncated, clamped at 0; the end in uint32 arithmetic"""
+    q = np.float64(t) / np.float64(nblk)
+    centre = float(Fraction(float(q)) * npos - max_deviation)          # float(Fraction) rounds to nearest even, once
+    lo = max(int(centre), 0)                                           # int() truncates toward zero, as the cast does
+    hi = min((lo + 2 * max_deviation) & 0xFFFFFFFF, npos)
+    return lo, hi
+
+
+def band_table(nblk, npos, max_deviation):
+    """int64 [nblk, 2]: the band of every block for a sequence of npos - 1 bases; for a code's own npos this is
+    decoder.band_table(...)[0] (tests/test_trellis_score_host.py)"""
+    return np.array([_band(t, nblk, npos, int(max_deviation)) for t in range(nblk)], dtype=np.int64).reshape(nblk, 2)
+
+
+def reference_score(post, bases, max_deviation, npos=None):
+    """The two scores (flip, flop; float32) with which the reference trellis ends on the base sequence `bases` (uint8 codes
+    0..3, or the characters ACGT) for a read of posteriors `post` (float32 [nblk, 40], .post layout).
+
+    Restated from the reference's recurrence restricted to one base sequence, npos = len(bases) + 1 positions:
+      buffers    two of [npos][8], all -inf; cur[0][k] = 0 for the eight states; the two swap at the start of every block;
+                 a block updates the positions of its band only (band_table) and nothing is ever cleared;
+      position 0 stays only: cur[0][k] = prev[0][k] + post[k * 8 + k] for a flip k, + post[32 + k] for a flop k;
+      p > 0      with b = bases[p - 1]: flip b = max(prev[p][b] + post[b * 8 + b], prev[p - 1][s] + post[b * 8 + s] over every
+                 s != b); flop b + 4 = max(prev[p][b + 4] + post[32 + b + 4], prev[p - 1][b] + post[32 + b]); the other six
+                 states of the position stay -inf;
+      result     (cur[npos - 1][b_last], cur[npos - 1][b_last + 4]) after the last block.
+    Every addition is one float32 addition and every maximum is exact, so there is no order to choose.
+    Refuses (ValueError) nblk < npos + 1 as the reference does ("Too small post matrix"), an empty sequence and a base code
+    above 3.  Posteriors are finite or -inf: NaN and +inf are outside the definition (the reference's heap and its
+    `!= -inf` tests give them a meaning that depends on the list size; tests/golden/*_nan*, *_posinf* pin the decoder there,
+    not this function)."""
+    post = np.ascontiguousarray(post, dtype=np.float32).reshape(-1, 40)
+    seq = as_codes(bases)
+    if npos is None:
+        npos = len(seq) + 1
+    if npos != len(seq) + 1 or len(seq) < 1:
+        raise ValueError("npos = len(bases) + 1, and at least one base")
+    nblk = post.shape[0]
+    if nblk < npos + 1:
+        raise ValueError("Too small post matrix: %d blocks for %d positions" % (nblk, npos))
+    if np.isnan(post).any() or np.isposinf(post).any():
+        raise ValueError("posteriors are finite or -inf")
+    buf = np.full((2, npos, 8), NEG, dtype=np.float32)
+    buf[0, 0, :] = 0
+    stay = np.array([k * 8 + k for k in range(4)] + [32 + k for k in range(4, 8)])
+    bands = band_table(nblk, npos, max_deviation)
+    for t in range(nblk):
+        prev, cur = buf[t & 1], buf[(t + 1) & 1]
+        row = post[t]
+        lo, hi = bands[t]
+        for p in range(lo, hi):
+            if p == 0:
+                cur[0] = prev[0] + row[stay]
+                continue
+            b = int(seq[p - 1])
+            flip = prev[p, b] + row[b * 8 + b]
+            for s in range(8):
+                if s != b:
+                    flip = max(flip, prev[p - 1, s] + row[b * 8 + s])
+            cur[p, b] = flip
+            cur[p, b + 4] = max(prev[p, b + 4] + row[32 + b + 4], prev[p - 1, b] + row[32 + b])
+    last = buf[nblk & 1, npos - 1]
+    b = int(seq[-1])
+    return np.float32(last[b]), np.float32(last[b + 4])
+
+
+def as_codes(bases):
+    """a base sequence as uint8 codes 0..3: codes, or the characters ACGT (str, bytes or their byte values)"""
+    if isinstance(bases, str):
+        bases = bases.encode("ascii")
+    a = np.frombuffer(bases, dtype=np.uint8) if isinstance(bases, (bytes, bytearray)) else np.asarray(bases, dtype=np.uint8)
+    a = a.reshape(-1).copy()
+    for code, ch in enumerate(b"ACGT"):
+        a[a == ch] = code
+    if (a > 3).any():
+        raise ValueError("a base is A, C, G, T or a code 0..3")
+    return a
+
+
+def message_bases(mem_conv, rate, msg_len, msgs, rc=False, sync_marker="", sync_period=0):
+    """The base sequence that a decode with this rc flag walks for each message: uint8 [n, oligo_len] (or [oligo_len]).
+    Forward it is encode().  A reverse-complement decode (:359-386: mirrored generators, complemented output bits, the
+    message's bits consumed from the far end and written back reversed, :826-836) reads the other strand: the forward
+    oligo reversed, every base complemented (3 - b) -- held to the oracle's lists on the _rc fixtures by
+    tests/test_trellis_score_host.py.  The messages are given as decode() returns them, in encode()'s bit order, whatever rc.
+    A sync marker does not change the sequence: its bits are part of the message (the decoder returns them in place), and
+    the encoder treats them like any other; the arguments only check that the code exists."""
+    _dec.code_info(mem_conv, rate, msg_len, rc, sync_marker, sync_period)
+    fwd = _dec.encode(mem_conv, rate, msg_len, msgs)
+    if not rc:
+        return fwd
+    return np.ascontiguousarray((3 - fwd)[..., ::-1])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the use: why did a read's list miss the truth?
+# ---------------------------------------------------------------------------------------------------------------
+
+def verdict(rank, banded, unbanded, list_scores, list_size):
+    """One read.  rank: place of the truth in the list or -1; banded, unbanded: max(flip, flop) of the truth under the
+    decoder's band and with the band off (None, None: the read was too short to score); list_scores: the list's scores.
+    The first that applies:
+      short_read       the read has fewer blocks than the code's positions + 1: neither the decoder nor the score takes it;
+      in_list          rank >= 0;
+      band             the band cost the truth its path: the banded score is -inf, or below the unbanded one;
+      list_too_short   the band changed nothing for the truth and it lost on score: a finite score, at most the last entry's
+                       of a FULL list, so a longer list reaches it;
+      band             what is left -- a finite score that a list with room to spare does not hold, or one above a full list's
+                       last entry: an exact list decoder cannot lose such a message, only the band's buffers that are never
+                       cleared can (a position outside the band keeps what it held), so the band decides here too."""
+    if banded is None:
+        return "short_read"
+    if rank >= 0:
+        return "in_list"
+    if banded == NEG or banded < unbanded:
+        return "band"
+    if len(list_scores) == list_size and banded <= list_scores[-1]:
+        return "list_too_short"
+    return "band"
+
+
+def truth_rank(msgs, truth):
+    """place of `truth` (uint8 [msg_len]) among the rows of msgs (uint8 [count, msg_len]), or -1"""
+    if isinstance(msgs, int) or len(msgs) == 0:
+        return -1
+    hit = np.flatnonzero((np.asarray(msgs) == np.asarray(truth, dtype=np.uint8)[None, :]).all(axis=1))
+    return int(hit[0]) if len(hit) else -1
+
+
+def truth_rows(dec, dev, first_block, n_blocks, results, truth_msgs, rc):
+    """The table of the tool for reads that are resident on the device (windows first_block / n_blocks of the buffer `dev`),
+    their decode results and their true messages: two score_bases_resident calls on the buffer the decode read, one under the
+    decoder's band and one with the band off.  -> [dict(rank, banded, unbanded, first, last, verdict)]"""
+    n = len(results)
+    sync = (dec._sync.decode() if dec._sync else "", dec._sync_period)
+    info = _dec.code_info(dec.mem_conv, dec.rate, dec.msg_len, False, *sync)
+    rc = np.zeros(n, bool) if rc is None else np.asarray(rc, dtype=bool)
+    ok = [i for i in range(n) if int(n_blocks[i]) >= info.nstate_pos + 1]
+    banded, unbanded = {}, {}
+    if ok:
+        seqs = [message_bases(dec.mem_conv, dec.rate, dec.msg_len, truth_msgs[i], bool(rc[i]), *sync) for i in ok]
+        pairs = [(i, k) for k, i in enumerate(ok)]
+        a = dec.score_bases_resident(dev, first_block, n_blocks, seqs, pairs)
+        b = dec.score_bases_resident(dev, first_block, n_blocks, seqs, pairs, max_deviation=dec.msg_len + dec.mem_conv + 1)
+        for k, i in enumerate(ok):
+            banded[i], unbanded[i] = np.float32(a[k].max()), np.float32(b[k].max())
+    rows = []
+    for i, res in enumerate(results):
+        msgs, scores = ((), ()) if isinstance(res, int) else res
+        rank = truth_rank(msgs, truth_msgs[i])
+        rows.append(dict(rank=rank, banded=banded.get(i), unbanded=unbanded.get(i),
+                         first=float(scores[0]) if len(scores) else float("nan"),
+                         last=float(scores[-1]) if len(scores) else float("nan"),
+                         verdict=verdict(rank, banded.get(i), unbanded.get(i), scores, dec.list_size)))
+    return rows
+
+
+def count_verdicts(rows):
+    return {v: sum(r["verdict"] == v for r in rows) for v in VERDICTS}
+
+
+def simulate_rows(dec, n, seed, first_read=0, **kw):
+    """Decoder.simulate_and_decode with the truth scored on the buffer the decode read, before it is freed: the reads never
+    leave the device -> (truth, results, rows)"""
+    def after(dev, off, truth, results, rc):
+        return truth_rows(dec, dev, off[:-1], np.diff(off), results, truth["msgs"], rc)
+    return dec.simulate_and_decode(n, seed, first_read, after=after, **kw)
+
+
+def write_table(rows, path):
+    with open(path, "w") as f:
+        f.write("read\trank\tbanded\tunbanded\tfirst\tlast\tverdict\n")
+        for i, r in enumerate(rows):
+            sc = lambda v: "nan" if v is None else repr(float(v))
+            f.write("%d\t%d\t%s\t%s\t%r\t%r\t%s\n" % (i, r["rank"], sc(r["banded"]), sc(r["unbanded"]), r["first"], r["last"],
+                                                    r["verdict"]))
+
+
+def summary_line(rows):
+    c = count_verdicts(rows)
+    return "truth score: %d reads, " % len(rows) + ", ".join("%s %d" % (v, c[v]) for v in VERDICTS)
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="Score the true message of every read on the decoder's trellis: why did a list miss it?")
+    p.add_argument("--mem_conv", type=int, default=11)
+    p.add_argument("--rate", type=int, default=5)
+    p.add_argument("--msg_len", type=int, default=180)
+    p.add_argument("--list_size", type=int, default=8)
+    p.add_argument("--max_deviation", type=int, default=20)
+    p.add_argument("--device", type=int, default=0)
+    p.add_argument("--out", "-P", default="trellis_score", help="prefix P: the table goes to P.truth.tsv")
+    p.add_argument("--simulate", type=int, default=0, metavar="N", help="N reads of the device simulator (Decoder.simulate)")
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--sub", type=float, default=None)
+    p.add_argument("--dele", type=float, default=None)
+    p.add_argument("--ins", type=float, default=None)
+    p.add_argument("--manifest", help="a text file, one read per line: <posterior file (.post)> <true message as 0/1> [rc: 0/1]")
+    return p
+
+
+def main(argv=None, out=sys.stdout):
+    args = build_parser().parse_args(argv)
+    if bool(args.manifest) == bool(args.simulate):
+        raise SystemExit("give --manifest FILE or --simulate N")
+    with _dec.Decoder(args.mem_conv, args.rate, args.msg_len, list_size=args.list_size, max_deviation=args.max_deviation,
+                      device=args.device) as dec:
+        if args.simulate:
+            kw = {k: getattr(args, k) for k in ("sub", "dele", "ins") if getattr(args, k) is not None}
+            _, _, rows = simulate_rows(dec, args.simulate, args.seed, **kw)
+        else:
+            posts, msgs, rc = [], [], []
+            for ln in open(args.manifest):
+                w = ln.split()
+                if not w:
+                    continue
+                posts.append(np.fromfile(w[0], dtype="<f4").reshape(-1, 40))
+                msgs.append(_dec.str_to_bits(w[1]))
+                rc.append(len(w) > 2 and w[2] == "1")
+            with dec.resident(posts) as (dev, off):
+                results = dec.decode_resident(dev, off, rc)
+                rows = truth_rows(dec, dev, off[:-1], np.diff(off), results, np.array(msgs, dtype=np.uint8), rc)
+    write_table(rows, args.out + ".truth.tsv")
+    print(summary_line(rows), file=out)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
