@@ -1054,11 +1054,11 @@ int lva_align_profile(int32_t device, const uint8_t* bases, const int64_t* first
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------
-// reads mapped to oligos (csrc/mp_kernels.hip; the definition is read_map.py).  The index is
-// built once and owned by the caller; a mapping call takes a device ordinal like the list consumers.  Built on the host
-// (lva_map_index_create, lva_map_index_create_pooled) its tables are host vectors that every mapping call uploads; built on
-// the device (lva_map_index_create_device, csrc/mi_kernels.hip) they are device memory of that ordinal until the index is
-// destroyed, the same bytes, and a mapping call uploads the reads alone.
+// reads mapped to oligos (csrc/mp_kernels.hip, csrc/mq_kernels.hip; the definition is
+// read_map.py).  Both mapping entry points run one body, map_stage; which of them was called decides the kernels.  The index is built once and owned by the caller; a mapping call takes a device ordinal like the list
+// consumers.  Built on the host (lva_map_index_create, lva_map_index_create_pooled) its tables are host vectors that every mapping
+// call uploads; built on the device (lva_map_index_create_device, csrc/mi_kernels.hip) they are device memory of that ordinal until
+// the index is destroyed, the same bytes, and a mapping call uploads the reads alone.
 // ---------------------------------------------------------------------------------------------
 struct lva_map_index {
   int32_t n_refs, ref_len, k, max_occ;   // ref_len: the longest oligo; every oligo's where ragged is not set
@@ -1086,22 +1086,11 @@ namespace {
 
 constexpr size_t kMpChunkBytes = (size_t)1 << 30;        // what the candidate lists of a chunk of reads may occupy on the device
 
-// everything lva_map_reads can refuse without the device
+// everything both mapping entry points can refuse without the device; the threshold and the flanks are each entry's own
 int map_args(const lva_map_index* idx, const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases, int32_t n_reads,
-             int32_t cands, int32_t min_votes, int32_t max_dist, int32_t chunk_reads, const int32_t* out) {
-  if (!idx || n_reads < 0 || chunk_reads < 0 || cands < 1 || cands > kMpMaxCands || min_votes < 1 || max_dist < 0) return LVA_ERR_ARG;
+             int32_t cands, int32_t min_votes, int32_t chunk_reads, const int32_t* out) {
+  if (!idx || n_reads < 0 || chunk_reads < 0 || cands < 1 || cands > kMpMaxCands || min_votes < 1) return LVA_ERR_ARG;
   if (n_reads > 0 && (!bases || !first_base || !n_bases || !out)) return LVA_ERR_ARG;
-  return Windows::check(first_base, n_bases, n_reads, kMaxRead);
-}
-
-// everything lva_map_reads_pooled can refuse without the device
-int map_pooled_args(const lva_map_index* idx, const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases, int32_t n_reads,
-                    int32_t cands, int32_t min_votes, const int32_t* max_dist, int32_t min_flank, int32_t chunk_reads, const int32_t* out,
-                    const int32_t* supp) {
-  if (!idx || n_reads < 0 || chunk_reads < 0 || cands < 1 || cands > kMpMaxCands || min_votes < 1 || min_flank < 0 || !max_dist) return LVA_ERR_ARG;
-  for (int32_t o = 0; o < idx->n_refs; ++o)
-    if (max_dist[o] < 0) return LVA_ERR_ARG;
-  if (n_reads > 0 && (!bases || !first_base || !n_bases || !out || (min_flank > 0 && !supp))) return LVA_ERR_ARG;
   return Windows::check(first_base, n_bases, n_reads, kMaxRead);
 }
 
@@ -1269,6 +1258,61 @@ struct IndexTables {
   }
 };
 
+// THE mapping call behind both entry points, which have checked their arguments: vote, distance and start per chunk of
+// reads, and for min_flank > 0 (the pooled entry alone) the same over the longer flank of every mapped read, into supp.
+// pooled: lva_map_reads_pooled called (the mq launchers, max_dist [n_refs], whatever the index); else lva_map_reads (the mp
+// launchers, max_dist [1] for every oligo of one length, no lens and no thresholds uploaded).
+int map_stage(int32_t device, const lva_map_index* idx, const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases,
+              int32_t n_reads, int32_t cands, int32_t min_votes, bool pooled, const int32_t* max_dist, int32_t min_flank,
+              int32_t chunk_reads, int32_t* out, int32_t* supp) {
+  if (idx->device >= 0 && idx->device != device) return LVA_ERR_ARG;       // the tables live on another device
+  if (n_reads == 0) return LVA_OK;
+  const size_t n = (size_t)n_reads;
+  const bool flanks = min_flank > 0;
+  Windows w;                                             // (outlives the call's frame)
+  Frame f;
+  if (const int so = f.open(device)) return so;
+  w.pack(f, bases, first_base, n_bases, n);              // every read, as given
+  size_t chunk = std::min(n, kMpChunkBytes / (kMpMaxCands * sizeof(uint64_t)));
+  if (chunk_reads > 0) chunk = std::min(chunk, (size_t)chunk_reads);
+  const IndexTables t(f, idx, pooled);
+  const auto d_max = pooled ? f.in(max_dist, (size_t)idx->n_refs) : Piece<int32_t>{};
+  const auto d_cand = f.scratch<uint64_t>(chunk * kMpMaxCands);
+  const auto d_out = f.out(out, 8 * n);
+  // the supplementary pass: per read of a chunk its flank as a window (offset, length) and the flank's place in the read's window
+  const auto d_supp = flanks ? f.out(supp, 8 * n) : Piece<int32_t>{};
+  Piece<int32_t> d_foff, d_flen, d_fshift;
+  if (pooled) {                                          // (empty without flanks)
+    d_foff = f.scratch<int32_t>(flanks ? chunk : 0);
+    d_flen = f.scratch<int32_t>(flanks ? chunk : 0);
+    d_fshift = f.scratch<int32_t>(flanks ? chunk : 0);
+  }
+  if (const int st = f.begin()) return st;
+  for (size_t a = 0; a < n; a += chunk) {                // a read's rows depend on the read alone: chunks change nothing
+    const int32_t c = (int32_t)std::min(chunk, n - a);
+    const Windows::Chunk x = w.from(a);
+    // the windows (off, len) of the chunk mapped into rows; shift: what a window's start adds to the start it reports
+    const auto map_windows = [&](const int32_t* off, const int32_t* len, const int32_t* shift, int32_t* rows) {
+      int e = launch_mp_vote(x.bases, off, len, c, t.offsets, t.lists, idx->k, idx->n_refs, min_votes, cands, d_cand, f.stream());
+      if (pooled) {
+        if (!e) e = launch_mq_verify(x.bases, off, len, c, d_cand, t.masks, t.lens, idx->ref_len, cands, d_max, rows, f.stream());
+        if (!e) e = launch_mq_start(x.bases, off, len, c, t.masks, t.lens, idx->ref_len, shift, rows, f.stream());
+      } else {
+        if (!e) e = launch_mp_verify(x.bases, off, len, c, d_cand, t.masks, idx->ref_len, cands, max_dist[0], rows, f.stream());
+        if (!e) e = launch_mp_start(x.bases, off, len, c, t.masks, idx->ref_len, rows, f.stream());
+      }
+      return e;
+    };
+    int e = map_windows(x.off, x.len, nullptr, d_out.ptr() + 8 * a);
+    if (!e && flanks) {
+      e = launch_mq_flank(x.off, x.len, c, d_out.ptr() + 8 * a, min_flank, d_foff, d_flen, d_fshift, f.stream());
+      if (!e) e = map_windows(d_foff, d_flen, d_fshift, d_supp.ptr() + 8 * a);
+    }
+    if (e) return launch_status(e);
+  }
+  return f.finish();
+}
+
 }  // namespace
 
 extern "C" {
@@ -1327,73 +1371,19 @@ int lva_map_index_info(const lva_map_index* idx, int64_t* kmers, int64_t* pairs,
 
 int lva_map_reads(int32_t device, const lva_map_index* idx, const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases,
                   int32_t n_reads, int32_t cands, int32_t min_votes, int32_t max_dist, int32_t chunk_reads, int32_t* out) {
-  if (map_args(idx, bases, first_base, n_bases, n_reads, cands, min_votes, max_dist, chunk_reads, out) != LVA_OK) return LVA_ERR_ARG;
+  if (map_args(idx, bases, first_base, n_bases, n_reads, cands, min_votes, chunk_reads, out) != LVA_OK || max_dist < 0) return LVA_ERR_ARG;
   if (idx->ragged) return LVA_ERR_ARG;                    // one ref_len for all: lva_map_reads_pooled takes the others
-  if (idx->device >= 0 && idx->device != device) return LVA_ERR_ARG;       // the tables live on another device
-  if (n_reads == 0) return LVA_OK;
-  const size_t n = (size_t)n_reads;
-  Windows w;                                             // (outlives the call's frame)
-  Frame f;
-  if (const int so = f.open(device)) return so;
-  w.pack(f, bases, first_base, n_bases, n);              // every read, as given
-  size_t chunk = std::min(n, kMpChunkBytes / (kMpMaxCands * sizeof(uint64_t)));
-  if (chunk_reads > 0) chunk = std::min(chunk, (size_t)chunk_reads);
-  const IndexTables t(f, idx, false);
-  const auto d_cand = f.scratch<uint64_t>(chunk * kMpMaxCands);
-  const auto d_out = f.out(out, 8 * n);
-  if (const int st = f.begin()) return st;
-  for (size_t a = 0; a < n; a += chunk) {                // a read's row depends on the read alone: chunks change nothing
-    const int32_t c = (int32_t)std::min(chunk, n - a);
-    const Windows::Chunk x = w.from(a);
-    int e = launch_mp_vote(x.bases, x.off, x.len, c, t.offsets, t.lists, idx->k, idx->n_refs, min_votes, cands, d_cand, f.stream());
-    if (!e) e = launch_mp_verify(x.bases, x.off, x.len, c, d_cand, t.masks, idx->ref_len, cands, max_dist, d_out.ptr() + 8 * a, f.stream());
-    if (!e) e = launch_mp_start(x.bases, x.off, x.len, c, t.masks, idx->ref_len, d_out.ptr() + 8 * a, f.stream());
-    if (e) return launch_status(e);
-  }
-  return f.finish();
+  return map_stage(device, idx, bases, first_base, n_bases, n_reads, cands, min_votes, false, &max_dist, 0, chunk_reads, out, nullptr);
 }
 
 int lva_map_reads_pooled(int32_t device, const lva_map_index* idx, const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases,
                          int32_t n_reads, int32_t cands, int32_t min_votes, const int32_t* max_dist, int32_t min_flank,
                          int32_t chunk_reads, int32_t* out, int32_t* supp) {
-  if (map_pooled_args(idx, bases, first_base, n_bases, n_reads, cands, min_votes, max_dist, min_flank, chunk_reads, out, supp) != LVA_OK)
-    return LVA_ERR_ARG;
-  if (idx->device >= 0 && idx->device != device) return LVA_ERR_ARG;       // the tables live on another device
-  if (n_reads == 0) return LVA_OK;
-  const size_t n = (size_t)n_reads, nr = (size_t)idx->n_refs;
-  const bool flanks = min_flank > 0;
-  Windows w;                                             // (outlives the call's frame)
-  Frame f;
-  if (const int so = f.open(device)) return so;
-  w.pack(f, bases, first_base, n_bases, n);              // every read, as given
-  size_t chunk = std::min(n, kMpChunkBytes / (kMpMaxCands * sizeof(uint64_t)));
-  if (chunk_reads > 0) chunk = std::min(chunk, (size_t)chunk_reads);
-  const IndexTables t(f, idx, true);
-  const auto d_max = f.in(max_dist, nr);
-  const auto d_cand = f.scratch<uint64_t>(chunk * kMpMaxCands);
-  const auto d_out = f.out(out, 8 * n);
-  // the supplementary pass: per read of a chunk its flank as a window (offset, length) and the flank's place in the read's window
-  const auto d_supp = flanks ? f.out(supp, 8 * n) : Piece<int32_t>{};
-  const auto d_foff = f.scratch<int32_t>(flanks ? chunk : 0), d_flen = f.scratch<int32_t>(flanks ? chunk : 0);
-  const auto d_fshift = f.scratch<int32_t>(flanks ? chunk : 0);
-  if (const int st = f.begin()) return st;
-  for (size_t a = 0; a < n; a += chunk) {                // a read's rows depend on the read alone: chunks change nothing
-    const int32_t c = (int32_t)std::min(chunk, n - a);
-    const Windows::Chunk x = w.from(a);
-    int32_t* o = d_out.ptr() + 8 * a;
-    int e = launch_mp_vote(x.bases, x.off, x.len, c, t.offsets, t.lists, idx->k, idx->n_refs, min_votes, cands, d_cand, f.stream());
-    if (!e) e = launch_mq_verify(x.bases, x.off, x.len, c, d_cand, t.masks, t.lens, idx->ref_len, cands, d_max, o, f.stream());
-    if (!e) e = launch_mq_start(x.bases, x.off, x.len, c, t.masks, t.lens, idx->ref_len, nullptr, o, f.stream());
-    if (!e && flanks) {
-      int32_t* s = d_supp.ptr() + 8 * a;
-      e = launch_mq_flank(x.off, x.len, c, o, min_flank, d_foff, d_flen, d_fshift, f.stream());
-      if (!e) e = launch_mp_vote(x.bases, d_foff, d_flen, c, t.offsets, t.lists, idx->k, idx->n_refs, min_votes, cands, d_cand, f.stream());
-      if (!e) e = launch_mq_verify(x.bases, d_foff, d_flen, c, d_cand, t.masks, t.lens, idx->ref_len, cands, d_max, s, f.stream());
-      if (!e) e = launch_mq_start(x.bases, d_foff, d_flen, c, t.masks, t.lens, idx->ref_len, d_fshift, s, f.stream());
-    }
-    if (e) return launch_status(e);
-  }
-  return f.finish();
+  if (map_args(idx, bases, first_base, n_bases, n_reads, cands, min_votes, chunk_reads, out) != LVA_OK) return LVA_ERR_ARG;
+  if (!max_dist || min_flank < 0 || (n_reads > 0 && min_flank > 0 && !supp)) return LVA_ERR_ARG;
+  for (int32_t o = 0; o < idx->n_refs; ++o)
+    if (max_dist[o] < 0) return LVA_ERR_ARG;
+  return map_stage(device, idx, bases, first_base, n_bases, n_reads, cands, min_votes, true, max_dist, min_flank, chunk_reads, out, supp);
 }
 
 }  // extern "C"
