@@ -109,7 +109,7 @@ const char *lva_version(void);
 /* LVA_ABI_VERSION of the library that was loaded.  It changes whenever a struct of this header changes size or layout
  * (5: lva_profile gained overflow_steps and working_bytes): a caller built against another value must not pass structs.
  * Entry points added since (lva_stream_*, lva_transpost_*, lva_device_download, lva_list_*, lva_demux_*, lva_kernel_plan,
- * lva_align_profile, lva_map_index_*, lva_map_reads, lva_map_reads_pooled, lva_score_bases*) change no struct and keep it at 5. */
+ * lva_align_profile, lva_map_index_*, lva_map_reads, lva_map_reads_pooled, lva_score_bases*, lva_trace_bases*) change no struct and keep it at 5. */
 #define LVA_ABI_VERSION 5
 int lva_abi_version(void);
 const char *lva_strerror(int code);
@@ -624,6 +624,37 @@ int lva_score_bases_device(lva_decoder *d, const float *post_dev, const int64_t 
 int lva_score_bases(lva_decoder *d, const float *post, const int64_t *row_offsets, int32_t n_reads, const uint8_t *bases,
                     const int64_t *first_base, const int32_t *n_bases, int32_t n_seqs, const int32_t *pairs, int32_t n_pairs,
                     uint32_t max_deviation, float *out);
+
+/* The traceback of the same trellis: WHERE the best path of a given base sequence runs on a read -- a segmentation of the
+ * read (the block at which each base begins) and, for a truth that the band cut off, where its path left the band.  The
+ * definition is trellis_score.py (reference_trace: the recurrence of reference_score, the predecessor that won recorded per
+ * cell -- a later candidate replaces an earlier one only if strictly greater, stay first, then the states below ascending --
+ * and the walk back, a position outside a block's band taken from two blocks earlier and counted as a stale hop); the
+ * kernels are csrc/st_kernels.hip (st_fill, st_walk).  Arguments as lva_score_bases*, and:
+ *   end            the state of the last position the walk starts in: 0 flip, 1 flop, -1 the larger score, flip on a tie;
+ *   scratch_limit  bytes of back-pointers on the device at a time (a pair needs n_blocks * min(2 * max_deviation, n + 1),
+ *                  rounded up to 16); the pairs go in chunks that fit, one after another; 0: 1 GiB.  The outputs do not
+ *                  depend on it;
+ *   stride         elements per row of out_enter and out_kind: at least the longest paired sequence;
+ *   out_score      float [n_pairs][2] = (flip, flop), lva_score_bases' bits;
+ *   out_enter      int32 [n_pairs][stride]: at [p - 1] the block whose transition moved the path into position p, p = 1 .. n;
+ *                  the unused tail of a row is -1;
+ *   out_kind       uint8 [n_pairs][stride]: 0 if position p was entered and held as flip, 1 as flop; the tail is 255;
+ *   out_info       int32 [n_pairs][4] = (end_state 0 / 1, start_state 0 .. 7 at position 0 before the first block, stale hops, 0).
+ * A pair whose chosen end score is -inf has no path: its rows are -1 and 255, end_state and start_state -1, stale hops 0.
+ * Refusals: lva_score_bases' in its order, then LVA_ERR_ARG for end outside -1 .. 1, a stride below the longest paired
+ * sequence, a null output with n_pairs > 0 and a single pair that needs more than scratch_limit -- all before anything is
+ * allocated; then LVA_ERR_BUSY while a decode stream is open.  n_pairs = 0 succeeds and touches nothing.  Complete on return;
+ * the decoder's profile is left alone. */
+int lva_trace_bases_device(lva_decoder *d, const float *post_dev, const int64_t *first_block, const int64_t *n_blocks,
+                           int32_t n_reads, const uint8_t *bases, const int64_t *first_base, const int32_t *n_bases,
+                           int32_t n_seqs, const int32_t *pairs, int32_t n_pairs, uint32_t max_deviation, int32_t end,
+                           uint64_t scratch_limit, int32_t stride, float *out_score, int32_t *out_enter, uint8_t *out_kind,
+                           int32_t *out_info);
+int lva_trace_bases(lva_decoder *d, const float *post, const int64_t *row_offsets, int32_t n_reads, const uint8_t *bases,
+                    const int64_t *first_base, const int32_t *n_bases, int32_t n_seqs, const int32_t *pairs, int32_t n_pairs,
+                    uint32_t max_deviation, int32_t end, uint64_t scratch_limit, int32_t stride, float *out_score,
+                    int32_t *out_enter, uint8_t *out_kind, int32_t *out_info);
 
 
 /* ---------------------------------------------------------------------------------------------

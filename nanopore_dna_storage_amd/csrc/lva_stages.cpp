@@ -1,6 +1,6 @@
 // lva_stages.cpp -- C ABI (include/lva_decoder.h) of the stages beside the list decoder: transition posteriors (N0), basecall
 // and barcode localisation (N3), demultiplexing (N3'), the consumers of a decoded list (N2), the Reed-Solomon outer code (N4),
-// reading-cost trials (N4'), the read simulator (S), the error profile (N5), read mapping (N6), the one-message trellis (N7).  No algorithm lives here: an entry point checks its arguments, then works
+// reading-cost trials (N4'), the read simulator (S), the error profile (N5), read mapping (N6), the one-message trellis and its traceback (N7).  No algorithm lives here: an entry point checks its arguments, then works
 // through one Frame (below): it declares its device pieces together with their host side, begins (allocate, upload),
 // launches, finishes (copy back, wait).
 #include <algorithm>
@@ -20,6 +20,7 @@
 #include "mq_kernels.h"
 #include "mi_kernels.h"
 #include "sc_kernels.h"
+#include "st_kernels.h"
 
 using namespace lva;
 
@@ -1424,17 +1425,45 @@ int score_args(const int64_t* first_block, const int64_t* n_blocks, int32_t n_re
   return LVA_OK;
 }
 
+// What a trace asks for beside the scores (lva_trace_bases*); a score call has none
+struct TraceOut {
+  int32_t end;                 // 0 flip, 1 flop, -1 the larger
+  uint64_t scratch_limit;      // bytes of back-pointers on the device at a time; 0: kStScratchDefault
+  int32_t stride;
+  int32_t* enter;
+  uint8_t* kind;
+  int32_t* info;
+};
+constexpr uint64_t kStScratchDefault = (uint64_t)1 << 30;
+
+// back-pointer bytes of one pair: [nblk][min(2 * max_deviation, positions)], padded to the 16 bytes a pair's rows start at
+uint32_t trace_width(uint32_t max_dev, int32_t n_bases) { return (uint32_t)std::min<uint64_t>(2 * (uint64_t)max_dev, (uint64_t)n_bases + 1); }
+uint64_t trace_bytes(uint32_t max_dev, int64_t nblk, int32_t n_bases) {
+  return ((uint64_t)nblk * trace_width(max_dev, n_bases) + 15) & ~(uint64_t)15;
+}
+
 // lva_score_bases (post on the host, read i = blocks [first_block[i], + n_blocks[i]) of it, T blocks in all: uploaded) and
-// lva_score_bases_device (post the caller's device buffer)
+// lva_score_bases_device (post the caller's device buffer); with tr, lva_trace_bases and lva_trace_bases_device: the same
+// pairs and band tables, st_fill and st_walk in place of sc_score, chunk by chunk of what the back-pointers may occupy
 int score_stage(lva_decoder* d, const float* post, size_t host_blocks, bool post_on_host, const int64_t* first_block,
                 const int64_t* n_blocks, int32_t n_reads, const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases,
-                int32_t n_seqs, const int32_t* pairs, int32_t n_pairs, uint32_t max_deviation, float* out) {
+                int32_t n_seqs, const int32_t* pairs, int32_t n_pairs, uint32_t max_deviation, float* out,
+                const TraceOut* tr = nullptr) {
   if (!d) return LVA_ERR_ARG;
   int st = score_args(first_block, n_blocks, n_reads, bases, first_base, n_bases, n_seqs, pairs, n_pairs, post, out);
   if (st != LVA_OK) return st;
+  const uint32_t max_dev = max_deviation == LVA_MAX_DEVIATION_DEFAULT ? d->max_dev : max_deviation;
+  if (tr) {                                              // the trace's own refusals, after the score's
+    const uint64_t limit = tr->scratch_limit ? tr->scratch_limit : kStScratchDefault;
+    if (tr->end < -1 || tr->end > 1 || tr->stride < 0) return LVA_ERR_ARG;
+    if (n_pairs > 0 && (!tr->enter || !tr->kind || !tr->info)) return LVA_ERR_ARG;
+    for (int32_t k = 0; k < n_pairs; ++k) {
+      if (n_bases[pairs[2 * k + 1]] > tr->stride) return LVA_ERR_ARG;
+      if (trace_bytes(max_dev, n_blocks[pairs[2 * k]], n_bases[pairs[2 * k + 1]]) > limit) return LVA_ERR_ARG;   // one pair alone
+    }
+  }
   st = stage_enter(d, n_pairs == 0);
   if (st != kRun) return st;
-  const uint32_t max_dev = max_deviation == LVA_MAX_DEVIATION_DEFAULT ? d->max_dev : max_deviation;
   // the pairs as the kernel reads them; one band table per (blocks, positions) that occurs
   Windows w;                                             // (these outlive the call's frame)
   std::vector<ScPair> sp((size_t)n_pairs);
@@ -1452,6 +1481,28 @@ int score_stage(lva_decoder* d, const float* post, size_t host_blocks, bool post
     if (i == 0 || keys[i].first != keys[i - 1].first) band_words += (size_t)(keys[i].first >> 32);
   if (band_words > kScMaxBandWords) return LVA_ERR_ARG;
   band.reserve(band_words);
+  // a trace: where each pair's back-pointers lie in its chunk's scratch, and the chunks, pairs [cuts[c], cuts[c + 1])
+  std::vector<StBp> sb;
+  std::vector<size_t> cuts;
+  uint64_t scratch_bytes = 0;
+  if (tr) {
+    const uint64_t limit = tr->scratch_limit ? tr->scratch_limit : kStScratchDefault;
+    sb.resize((size_t)n_pairs);
+    cuts.push_back(0);
+    uint64_t in_chunk = 0;
+    for (int32_t k = 0; k < n_pairs; ++k) {
+      const int32_t r = pairs[2 * k], s = pairs[2 * k + 1];
+      const uint64_t need = trace_bytes(max_dev, n_blocks[r], n_bases[s]);
+      if (in_chunk + need > limit) {                     // (need <= limit: checked above)
+        cuts.push_back((size_t)k);
+        in_chunk = 0;
+      }
+      sb[k] = StBp{in_chunk, trace_width(max_dev, n_bases[s]), 0};
+      in_chunk += need;
+      scratch_bytes = std::max(scratch_bytes, in_chunk);
+    }
+    cuts.push_back((size_t)n_pairs);
+  }
   Frame f(d->stream);
   w.pack(f, bases, first_base, n_bases, (size_t)n_seqs);
   for (size_t i = 0; i < keys.size(); ++i) {
@@ -1469,9 +1520,30 @@ int score_stage(lva_decoder* d, const float* post, size_t host_blocks, bool post
   const auto d_pairs = f.in(sp.data(), sp.size());
   const auto d_band = f.in(band.data(), band.size());
   const auto d_out = f.out(out, 2 * (size_t)n_pairs);
+  if (!tr) {
+    if ((st = f.begin()) != LVA_OK) return st;
+    const int e = launch_sc_score(post_on_host ? up.ptr() : post, w.bases, d_pairs, d_band, n_pairs, max_len, d_out, f.stream());
+    if (e) return launch_status(e);
+    return f.finish();
+  }
+  const size_t rows = (size_t)n_pairs * (size_t)tr->stride;
+  const auto d_bp = f.in(sb.data(), sb.size());
+  const auto d_enter = f.out(tr->enter, rows);
+  const auto d_kind = f.out(tr->kind, rows);
+  const auto d_info = f.out(tr->info, 4 * (size_t)n_pairs);
+  const auto d_scratch = f.scratch<uint8_t>((size_t)scratch_bytes);
   if ((st = f.begin()) != LVA_OK) return st;
-  const int e = launch_sc_score(post_on_host ? up.ptr() : post, w.bases, d_pairs, d_band, n_pairs, max_len, d_out, f.stream());
-  if (e) return launch_status(e);
+  const float* d_post = post_on_host ? up.ptr() : post;
+  for (size_t c = 0; c + 1 < cuts.size(); ++c) {         // a pair's outputs depend on the pair alone: chunks change nothing
+    const size_t a = cuts[c];
+    const int32_t n = (int32_t)(cuts[c + 1] - a);
+    int e = launch_st_fill(d_post, w.bases, d_pairs.ptr() + a, d_bp.ptr() + a, d_band, n, max_len, d_scratch, d_out.ptr() + 2 * a,
+                           f.stream());
+    if (!e) e = launch_st_walk(w.bases, d_pairs.ptr() + a, d_bp.ptr() + a, d_band, n, d_scratch, d_out.ptr() + 2 * a, tr->end, tr->stride,
+                               d_enter.ptr() + a * (size_t)tr->stride, d_kind.ptr() + a * (size_t)tr->stride, d_info.ptr() + 4 * a,
+                               f.stream());
+    if (e) return launch_status(e);
+  }
   return f.finish();
 }
 
@@ -1496,6 +1568,29 @@ int lva_score_bases(lva_decoder* d, const float* post, const int64_t* row_offset
   const std::vector<int64_t> nb(len.begin(), len.end());
   return score_stage(d, post, T, true, row_offsets, nb.data(), n_reads, bases, first_base, n_bases, n_seqs, pairs, n_pairs,
                      max_deviation, out);
+}
+
+int lva_trace_bases_device(lva_decoder* d, const float* post_dev, const int64_t* first_block, const int64_t* n_blocks, int32_t n_reads,
+                           const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases, int32_t n_seqs,
+                           const int32_t* pairs, int32_t n_pairs, uint32_t max_deviation, int32_t end, uint64_t scratch_limit,
+                           int32_t stride, float* out_score, int32_t* out_enter, uint8_t* out_kind, int32_t* out_info) {
+  const TraceOut tr{end, scratch_limit, stride, out_enter, out_kind, out_info};
+  return score_stage(d, post_dev, 0, false, first_block, n_blocks, n_reads, bases, first_base, n_bases, n_seqs, pairs, n_pairs,
+                     max_deviation, out_score, &tr);
+}
+
+int lva_trace_bases(lva_decoder* d, const float* post, const int64_t* row_offsets, int32_t n_reads, const uint8_t* bases,
+                    const int64_t* first_base, const int32_t* n_bases, int32_t n_seqs, const int32_t* pairs, int32_t n_pairs,
+                    uint32_t max_deviation, int32_t end, uint64_t scratch_limit, int32_t stride, float* out_score,
+                    int32_t* out_enter, uint8_t* out_kind, int32_t* out_info) {
+  if (!d || n_reads < 0 || !row_offsets) return LVA_ERR_ARG;
+  size_t T = 0;
+  if (check_offsets(row_offsets, n_reads, &T) != LVA_OK) return LVA_ERR_ARG;
+  const std::vector<int32_t> len = read_lengths(row_offsets, n_reads);
+  const std::vector<int64_t> nb(len.begin(), len.end());
+  const TraceOut tr{end, scratch_limit, stride, out_enter, out_kind, out_info};
+  return score_stage(d, post, T, true, row_offsets, nb.data(), n_reads, bases, first_base, n_bases, n_seqs, pairs, n_pairs,
+                     max_deviation, out_score, &tr);
 }
 
 }  // extern "C"

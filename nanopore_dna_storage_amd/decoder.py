@@ -159,6 +159,7 @@ class Decoder:
         check(self._L.lva_decoder_create(ctypes.byref(cfg), ctypes.byref(h)))
         self._h = h
         self.mem_conv, self.rate, self.msg_len, self.list_size = mem_conv, rate, msg_len, list_size
+        self.max_deviation = max_deviation               # None: the band is off
         self.device = device
         self._sync_period = sync_period
 
@@ -290,8 +291,10 @@ class Decoder:
         return out
 
     # --- what a given sequence or message scores on a read (trellis_score.py is the definition) -----
-    def _score(self, fn, where, n_reads, seqs, pairs, max_deviation):
-        """the one score call: `where` is what the entry point takes between the decoder and n_reads"""
+    @staticmethod
+    def _score_args(seqs, pairs, max_deviation):
+        """what the score and the trace entry points take after n_reads, up to max_deviation: (the arguments, the arrays they
+        point into, the sequence lengths, the number of pairs)"""
         from .trellis_score import as_codes
         seqs = [as_codes(s) for s in seqs]
         lens = np.array([len(s) for s in seqs], dtype=np.int32)
@@ -299,11 +302,27 @@ class Decoder:
         first[1:] = np.cumsum(lens[:-1], dtype=np.int64)
         bases = np.concatenate(seqs + [np.zeros(1, np.uint8)])
         pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
-        out = np.zeros((len(pr), 2), np.float32)
         md = _lib.MAX_DEVIATION_DEFAULT if max_deviation is None else int(max_deviation)
-        self._check(fn(self._h, *where, n_reads, bases.ctypes.data, first.ctypes.data, lens.ctypes.data, len(seqs), pr.ctypes.data,
-                       len(pr), md, out.ctypes.data))
+        args = (bases.ctypes.data, first.ctypes.data, lens.ctypes.data, len(seqs), pr.ctypes.data, len(pr), md)
+        return args, (bases, first, pr), lens, len(pr)
+
+    def _score(self, fn, where, n_reads, seqs, pairs, max_deviation):
+        """the one score call: `where` is what the entry point takes between the decoder and n_reads"""
+        args, _keep, _, n = self._score_args(seqs, pairs, max_deviation)
+        out = np.zeros((n, 2), np.float32)
+        self._check(fn(self._h, *where, n_reads, *args, out.ctypes.data))
         return out
+
+    def _trace(self, fn, where, n_reads, seqs, pairs, max_deviation, end, scratch_limit):
+        """the one trace call, after _score"""
+        args, _keep, lens, n = self._score_args(seqs, pairs, max_deviation)
+        stride = int(lens.max()) if len(lens) else 1
+        score, info = np.zeros((n, 2), np.float32), np.zeros((n, 4), np.int32)
+        enter, kind = np.full((n, stride), -1, np.int32), np.full((n, stride), 255, np.uint8)
+        self._check(fn(self._h, *where, n_reads, *args, int(end), int(scratch_limit), stride, score.ctypes.data, enter.ctypes.data,
+                       kind.ctypes.data, info.ctypes.data))
+        return dict(score=score, enter=enter, kind=kind, end_state=info[:, 0].copy(), start_state=info[:, 1].copy(),
+                    n_stale=info[:, 2].copy())
 
     def score_bases(self, posts, seqs, pairs, max_deviation=None):
         """The reference trellis restricted to one base sequence, per (read, sequence) pair: posts as decode() takes them,
@@ -327,6 +346,10 @@ class Decoder:
         encode()'s bit order (rows of a decoded list as they are), pairs [(read, message)], rc an optional bool per READ (the
         flag its decode takes; a message is encoded for the orientation of every read it is paired with).
         -> float32 [n_pairs, 2]; every score of decode()'s list for a read is one of the two values of its message."""
+        return self.score_bases(posts, *self._message_pairs(posts, msgs, pairs, rc))
+
+    def _message_pairs(self, posts, msgs, pairs, rc):
+        """(sequences, pairs into them) of score_messages' and trace_messages' arguments"""
         from .trellis_score import message_bases
         msgs = np.ascontiguousarray(msgs, dtype=np.uint8).reshape(-1, self.msg_len)
         pr = np.array(pairs, dtype=np.int32).reshape(-1, 2)          # a copy: the message indices become sequence indices below
@@ -346,7 +369,32 @@ class Decoder:
                 at = dict(zip(use.tolist(), range(len(seqs), len(seqs) + len(use))))
                 seqs += list(enc)
                 pr[flip == want, 1] = [at[m] for m in pr[flip == want, 1].tolist()]
-        return self.score_bases(posts, seqs, pr)
+        return seqs, pr
+
+    # --- the traceback of the same trellis (trellis_score.reference_trace is the definition; csrc/st_kernels.hip) --------
+    def trace_bases(self, posts, seqs, pairs, max_deviation=None, end=-1, scratch_limit=0):
+        """The best path of a base sequence on a read, per (read, sequence) pair; arguments as score_bases, end: the state of
+        the last position the walk starts in (0 flip, 1 flop, -1 the larger score, flip on a tie), scratch_limit: bytes of
+        back-pointers on the device at a time (0: 1 GiB; the result does not depend on it).
+        -> dict of arrays, byte for byte trellis_score.reference_trace(posts[r], seqs[s], max_deviation, end):
+        score float32 [n_pairs, 2] (score_bases' bits); enter int32 [n_pairs, longest sequence], PADDED with -1: enter[k, p - 1]
+        is the block whose transition moved the path of pair k into position p, for p up to the length of the pair's sequence;
+        kind uint8, padded with 255 (0: the position is held as flip, 1: as flop); start_state, end_state, n_stale int32
+        [n_pairs].  A pair without a path (an end score of -inf) has enter -1, kind 255 and both states -1."""
+        flat, off = self._pack(posts)
+        return self._trace(self._L.lva_trace_bases, (flat.ctypes.data, off.ctypes.data), len(off) - 1, seqs, pairs, max_deviation,
+                           end, scratch_limit)
+
+    def trace_bases_resident(self, dev_ptr, first_block, n_blocks, seqs, pairs, max_deviation=None, end=-1, scratch_limit=0):
+        """trace_bases() on windows of a resident posterior buffer, as score_bases_resident reads them"""
+        fb = np.ascontiguousarray(first_block, dtype=np.int64)
+        nb = np.ascontiguousarray(n_blocks, dtype=np.int64)
+        return self._trace(self._L.lva_trace_bases_device, (dev_ptr, fb.ctypes.data, nb.ctypes.data), len(fb), seqs, pairs,
+                           max_deviation, end, scratch_limit)
+
+    def trace_messages(self, posts, msgs, pairs, rc=None, end=-1, scratch_limit=0):
+        """trace_bases() for messages under this decoder's code and max_deviation; msgs, pairs and rc as score_messages"""
+        return self.trace_bases(posts, *self._message_pairs(posts, msgs, pairs, rc), end=end, scratch_limit=scratch_limit)
 
     # --- SURVEY 8(f) row N3: basecall of the posterior matrix + barcode localisation ------------
     def _basecall(self, fn, src, off):

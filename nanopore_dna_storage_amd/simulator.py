@@ -146,6 +146,7 @@ def report(args, reads, results, out=sys.stdout, truth_rows=None):
         from . import trellis_score
         for verdict, count in trellis_score.count_verdicts(truth_rows).items():
             stats["Number truth " + verdict] = count
+        stats["Number truth band dev_needed"] = trellis_score.band_dev_needed(truth_rows)    # the max_deviation that keeps them all
     print("Summary statistics:", file=out)
     for k, v in stats.items():
         print(k + ":", v, file=out)

@@ -16,10 +16,13 @@ message, bit for bit (tests/test_trellis_score_host.py holds reference_score to 
   reference_score   the definition, plain numpy (this file is to csrc/sc_kernels.hip what read_map.py is to mp_kernels.hip);
   message_bases     the base sequence that a decode with a given rc flag walks for a message;
   Decoder.score_bases / score_bases_resident / score_messages (decoder.py)   the same on the device, bit for bit;
-  verdicts, main    the use: why did the list of a read miss the truth?
+  reference_trace   the definition of the traceback (csrc/st_kernels.hip): the best path of a sequence on a read, as the block
+                    at which each position is entered; deviation_needed, left_band_at: what a band does to such a path;
+  Decoder.trace_bases / trace_bases_resident / trace_messages   the same on the device, byte for byte;
+  verdicts, main    the use: why did the list of a read miss the truth, and which max_deviation would have kept it?
 
     python -m nanopore_dna_storage_amd.trellis_score --simulate 2000 --seed 1 --mem_conv 11 --rate 5 --msg_len 180 \
-        --list_size 8 --max_deviation 20 --out run        # -> run.truth.tsv and a summary line
+        --list_size 8 --max_deviation 20 --out run        # -> run.truth.tsv and a summary line; --trace: run.trace.tsv too
 """
 import argparse
 import sys
@@ -101,6 +104,124 @@ def reference_score(post, bases, max_deviation, npos=None):
     return np.float32(last[b]), np.float32(last[b + 4])
 
 
+def reference_trace(post, bases, max_deviation, end=-1):
+    """The best path of the base sequence `bases` on a read: reference_score's recurrence (same buffers, bands, float32
+    additions, parity buffers that are never cleared) with, for every cell a block writes, the predecessor that won -- and
+    the walk back from the last position after the last block.  The definition of csrc/st_kernels.hip.
+
+    Tie rule: a later candidate replaces an earlier one only if it is strictly greater.  The candidates of a flip: the stay,
+    then the states s of the position below, ascending; of a flop: the stay, then the step from the flip below; position 0
+    only stays.
+    Walk: from the last position, in flip (end = 0), flop (end = 1) or the larger of the two, flip on a tie (end = -1).
+    With (t, p) the cell of position p after block t: p inside block t's band follows the recorded choice -- a stay to
+    (t - 1, p), an entry to (t - 1, p - 1) in the recorded state; p outside the band holds what it held two blocks earlier:
+    to (t - 2, p), one stale hop.  The walk ends at t = -1, at position 0 in one of the eight start states.
+    -> dict(score = (flip, flop), reference_score's bits; enter int32 [len]: at [p - 1] the block whose transition moved the
+    path into position p; kind uint8 [len]: 0 the position was entered and held as flip, 1 as flop; start_state 0..7;
+    end_state 0 or 1; n_stale).  A chosen end score of -inf is no path: enter -1, kind 255, both states -1, n_stale 0.
+    Refuses what reference_score refuses, and an end outside -1..1."""
+    if end not in (-1, 0, 1):
+        raise ValueError("end is 0 (flip), 1 (flop) or -1 (the larger)")
+    post = np.ascontiguousarray(post, dtype=np.float32).reshape(-1, 40)
+    seq = as_codes(bases)
+    npos, nblk = len(seq) + 1, post.shape[0]
+    if len(seq) < 1:
+        raise ValueError("at least one base")
+    if nblk < npos + 1:
+        raise ValueError("Too small post matrix: %d blocks for %d positions" % (nblk, npos))
+    if np.isnan(post).any() or np.isposinf(post).any():
+        raise ValueError("posteriors are finite or -inf")
+    buf = np.full((2, npos, 8), NEG, dtype=np.float32)
+    buf[0, 0, :] = 0
+    stay = np.array([k * 8 + k for k in range(4)] + [32 + k for k in range(4, 8)])
+    bands = band_table(nblk, npos, max_deviation)
+    won = np.zeros((nblk, npos, 2), np.uint8)              # [t, p] = (flip: 0 stay, 1 + s from state s; flop: 0 stay, 1 step)
+    for t in range(nblk):
+        prev, cur = buf[t & 1], buf[(t + 1) & 1]
+        row = post[t]
+        lo, hi = bands[t]
+        for p in range(lo, hi):
+            if p == 0:
+                cur[0] = prev[0] + row[stay]
+                continue
+            b = int(seq[p - 1])
+            flip, choice = prev[p, b] + row[b * 8 + b], 0
+            for s in range(8):
+                if s != b:
+                    v = prev[p - 1, s] + row[b * 8 + s]
+                    if v > flip:
+                        flip, choice = v, 1 + s
+            flop, step = prev[p, b + 4] + row[32 + b + 4], prev[p - 1, b] + row[32 + b]
+            won[t, p, 0] = choice
+            if step > flop:
+                flop, won[t, p, 1] = step, 1
+            cur[p, b], cur[p, b + 4] = flip, flop
+    last = buf[nblk & 1, npos - 1]
+    b = int(seq[-1])
+    score = (np.float32(last[b]), np.float32(last[b + 4]))
+    k = int(score[1] > score[0]) if end < 0 else end
+    out = dict(score=score, enter=np.full(npos - 1, -1, np.int32), kind=np.full(npos - 1, 255, np.uint8), start_state=-1,
+               end_state=-1, n_stale=0)
+    if score[k] == NEG:
+        return out
+    out["end_state"] = k
+    t, p = nblk - 1, npos - 1
+    while t >= 0:
+        lo, hi = bands[t]
+        if not lo <= p < hi:
+            out["n_stale"] += 1
+            t -= 2
+            continue
+        choice = int(won[t, p, k])
+        if p > 0 and choice:
+            out["enter"][p - 1], out["kind"][p - 1] = t, k
+            state = int(seq[p - 1]) if k else choice - 1   # a flop is entered from the flip of the same base below
+            if p == 1:
+                out["start_state"] = state
+            k = int(state >= 4)
+            p -= 1
+        t -= 1
+    assert t == -1 and p == 0 and out["start_state"] >= 0    # a finite score has a path of finite cells back to the start
+    return out
+
+
+def positions_after(enter, nblk):
+    """int64 [nblk]: the position p_t at which a path stands after block t -- the number of positions with enter <= t"""
+    enter = np.asarray(enter, dtype=np.int64)
+    return np.searchsorted(np.sort(enter), np.arange(nblk), side="right")
+
+
+def band_contains(enter, nblk, max_deviation):
+    """does the band of max_deviation hold the path at every block: lo(t) <= p_t < hi(t), npos = len(enter) + 1?"""
+    bands = band_table(nblk, len(enter) + 1, max_deviation)
+    at = positions_after(enter, nblk)
+    return bool(((bands[:, 0] <= at) & (at < bands[:, 1])).all())
+
+
+def deviation_needed(enter, nblk):
+    """The smallest max_deviation D >= 1 whose band contains a path without stale hops (enter as reference_trace gives it, every
+    entry >= 0).  Containment is monotone in D -- lo falls and hi rises with D -- and D = len(enter) + 1 contains every path
+    (lo = 0, hi = npos): a bisection."""
+    if len(enter) < 1 or np.min(enter) < 0:
+        raise ValueError("a path enters every position")
+    lo, hi = 1, len(enter) + 1                               # the answer is in [lo, hi]
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if band_contains(enter, nblk, mid):
+            hi = mid
+        else:
+            lo = mid + 1
+    return lo
+
+
+def left_band_at(enter, nblk, max_deviation):
+    """the first block at which the path lies outside the band of max_deviation, or -1"""
+    bands = band_table(nblk, len(enter) + 1, max_deviation)
+    at = positions_after(enter, nblk)
+    out = np.flatnonzero((at < bands[:, 0]) | (at >= bands[:, 1]))
+    return int(out[0]) if len(out) else -1
+
+
 def as_codes(bases):
     """a base sequence as uint8 codes 0..3: codes, or the characters ACGT (str, bytes or their byte values)"""
     if isinstance(bases, str):
@@ -167,20 +288,31 @@ def truth_rank(msgs, truth):
 def truth_rows(dec, dev, first_block, n_blocks, results, truth_msgs, rc):
     """The table of the tool for reads that are resident on the device (windows first_block / n_blocks of the buffer `dev`),
     their decode results and their true messages: two score_bases_resident calls on the buffer the decode read, one under the
-    decoder's band and one with the band off.  -> [dict(rank, banded, unbanded, first, last, verdict)]"""
+    decoder's band and one with the band off, and one trace_bases_resident call with the band off -- where the truth's best
+    path runs.  -> [dict(rank, banded, unbanded, first, last, verdict, dev_needed, left_band_at, trace)]: dev_needed the
+    smallest max_deviation whose band holds that path (deviation_needed; nan for a short read and a truth without a path),
+    left_band_at the first block at which the path lies outside the decoder's band or -1, trace = dict(start_state,
+    end_state, enter) of the path or None."""
     n = len(results)
     sync = (dec._sync.decode() if dec._sync else "", dec._sync_period)
     info = _dec.code_info(dec.mem_conv, dec.rate, dec.msg_len, False, *sync)
     rc = np.zeros(n, bool) if rc is None else np.asarray(rc, dtype=bool)
     ok = [i for i in range(n) if int(n_blocks[i]) >= info.nstate_pos + 1]
-    banded, unbanded = {}, {}
+    banded, unbanded, path = {}, {}, {}
     if ok:
         seqs = [message_bases(dec.mem_conv, dec.rate, dec.msg_len, truth_msgs[i], bool(rc[i]), *sync) for i in ok]
         pairs = [(i, k) for k, i in enumerate(ok)]
         a = dec.score_bases_resident(dev, first_block, n_blocks, seqs, pairs)
-        b = dec.score_bases_resident(dev, first_block, n_blocks, seqs, pairs, max_deviation=dec.msg_len + dec.mem_conv + 1)
+        off_band = dec.msg_len + dec.mem_conv + 1
+        b = dec.score_bases_resident(dev, first_block, n_blocks, seqs, pairs, max_deviation=off_band)
+        tr = dec.trace_bases_resident(dev, first_block, n_blocks, seqs, pairs, max_deviation=off_band)
+        md = dec.max_deviation if dec.max_deviation is not None else off_band
         for k, i in enumerate(ok):
             banded[i], unbanded[i] = np.float32(a[k].max()), np.float32(b[k].max())
+            if tr["end_state"][k] >= 0 and tr["n_stale"][k] == 0:
+                enter, nblk = tr["enter"][k, :len(seqs[k])], int(n_blocks[i])
+                path[i] = dict(dev_needed=deviation_needed(enter, nblk), left_band_at=left_band_at(enter, nblk, md),
+                               trace=dict(start_state=int(tr["start_state"][k]), end_state=int(tr["end_state"][k]), enter=enter))
     rows = []
     for i, res in enumerate(results):
         msgs, scores = ((), ()) if isinstance(res, int) else res
@@ -188,7 +320,8 @@ def truth_rows(dec, dev, first_block, n_blocks, results, truth_msgs, rc):
         rows.append(dict(rank=rank, banded=banded.get(i), unbanded=unbanded.get(i),
                          first=float(scores[0]) if len(scores) else float("nan"),
                          last=float(scores[-1]) if len(scores) else float("nan"),
-                         verdict=verdict(rank, banded.get(i), unbanded.get(i), scores, dec.list_size)))
+                         verdict=verdict(rank, banded.get(i), unbanded.get(i), scores, dec.list_size),
+                         **path.get(i, dict(dev_needed=float("nan"), left_band_at=-1, trace=None))))
     return rows
 
 
@@ -205,17 +338,43 @@ def simulate_rows(dec, n, seed, first_read=0, **kw):
 
 
 def write_table(rows, path):
+    """P.truth.tsv: the seven columns of the scores, and after them dev_needed and left_band_at where the rows carry the trace
+    of the truth (truth_rows' do)"""
+    traced = bool(rows) and all("dev_needed" in r for r in rows)
     with open(path, "w") as f:
-        f.write("read\trank\tbanded\tunbanded\tfirst\tlast\tverdict\n")
+        f.write("read\trank\tbanded\tunbanded\tfirst\tlast\tverdict" + ("\tdev_needed\tleft_band_at" if traced else "") + "\n")
         for i, r in enumerate(rows):
             sc = lambda v: "nan" if v is None else repr(float(v))
-            f.write("%d\t%d\t%s\t%s\t%r\t%r\t%s\n" % (i, r["rank"], sc(r["banded"]), sc(r["unbanded"]), r["first"], r["last"],
-                                                    r["verdict"]))
+            f.write("%d\t%d\t%s\t%s\t%r\t%r\t%s" % (i, r["rank"], sc(r["banded"]), sc(r["unbanded"]), r["first"], r["last"],
+                                                  r["verdict"]))
+            if traced:
+                f.write("\t%s\t%d" % ("nan" if r["dev_needed"] != r["dev_needed"] else "%d" % r["dev_needed"], r["left_band_at"]))
+            f.write("\n")
 
 
-def summary_line(rows):
+def write_trace(rows, path):
+    """P.trace.tsv, one row per read: read, start_state, end_state and the block at which the truth's unbanded path enters each
+    position, comma-separated (a read without a path: -1, -1 and nothing)"""
+    with open(path, "w") as f:
+        f.write("read\tstart_state\tend_state\tenter\n")
+        for i, r in enumerate(rows):
+            t = r.get("trace")
+            f.write("%d\t%d\t%d\t%s\n" % ((i, t["start_state"], t["end_state"], ",".join(map(str, t["enter"].tolist()))) if t
+                                        else (i, -1, -1, "")))
+
+
+def band_dev_needed(rows):
+    """the largest dev_needed among the reads with verdict band whose truth has a path (0: no such read): the max_deviation
+    that would have kept every one of them"""
+    need = [r["dev_needed"] for r in rows if r["verdict"] == "band" and r.get("dev_needed", float("nan")) == r.get("dev_needed")]
+    return int(max(need)) if need else 0
+
+
+def summary_line(rows, dev_needed=False):
+    """the count per verdict; dev_needed: and the largest dev_needed among the reads with verdict band (band_dev_needed)"""
     c = count_verdicts(rows)
-    return "truth score: %d reads, " % len(rows) + ", ".join("%s %d" % (v, c[v]) for v in VERDICTS)
+    line = "truth score: %d reads, " % len(rows) + ", ".join("%s %d" % (v, c[v]) for v in VERDICTS)
+    return line + (", band dev_needed %d" % band_dev_needed(rows) if dev_needed else "")
 
 
 def build_parser():
@@ -232,6 +391,9 @@ def build_parser():
     p.add_argument("--sub", type=float, default=None)
     p.add_argument("--dele", type=float, default=None)
     p.add_argument("--ins", type=float, default=None)
+    p.add_argument("--trace", action="store_true",
+                   help="also write P.trace.tsv (the truth's unbanded path per read: start_state, end_state, the block at which "
+                        "each position is entered) and add the largest dev_needed among the band reads to the summary line")
     p.add_argument("--manifest", help="a text file, one read per line: <posterior file (.post)> <true message as 0/1> [rc: 0/1]")
     return p
 
@@ -258,7 +420,9 @@ def main(argv=None, out=sys.stdout):
                 results = dec.decode_resident(dev, off, rc)
                 rows = truth_rows(dec, dev, off[:-1], np.diff(off), results, np.array(msgs, dtype=np.uint8), rc)
     write_table(rows, args.out + ".truth.tsv")
-    print(summary_line(rows), file=out)
+    if args.trace:
+        write_trace(rows, args.out + ".trace.tsv")
+    print(summary_line(rows, dev_needed=args.trace), file=out)
     return 0
 
 
