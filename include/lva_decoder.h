@@ -109,7 +109,8 @@ const char *lva_version(void);
 /* LVA_ABI_VERSION of the library that was loaded.  It changes whenever a struct of this header changes size or layout
  * (5: lva_profile gained overflow_steps and working_bytes): a caller built against another value must not pass structs.
  * Entry points added since (lva_stream_*, lva_transpost_*, lva_device_download, lva_list_*, lva_demux_*, lva_kernel_plan,
- * lva_align_profile, lva_map_index_*, lva_map_reads, lva_map_reads_pooled, lva_score_bases*, lva_trace_bases*) change no struct and keep it at 5. */
+ * lva_align_profile, lva_map_index_*, lva_map_reads, lva_map_reads_pooled, lva_score_bases*, lva_trace_bases*,
+ * lva_forward_bases*) change no struct and keep it at 5. */
 #define LVA_ABI_VERSION 5
 int lva_abi_version(void);
 const char *lva_strerror(int code);
@@ -624,6 +625,30 @@ int lva_score_bases_device(lva_decoder *d, const float *post_dev, const int64_t 
 int lva_score_bases(lva_decoder *d, const float *post, const int64_t *row_offsets, int32_t n_reads, const uint8_t *bases,
                     const int64_t *first_base, const int32_t *n_bases, int32_t n_seqs, const int32_t *pairs, int32_t n_pairs,
                     uint32_t max_deviation, float *out);
+
+/* The forward score of the same trellis: what ALL alignments of a given base sequence weigh on a read -- the log of the sum,
+ * over every path of the one-message trellis, of exp(the path's score).  A softmax of logaddexp(flip, flop) over the entries
+ * of a read's list is the posterior of each entry given the read, restricted to the list.  The definition is
+ * trellis_score.py (reference_forward; forward_total, list_posterior); the kernel is csrc/fw_kernels.hip.  Arguments,
+ * out = float [n_pairs][2] = (flip, flop), refusals and their order are lva_score_bases*'s.  Two differences from the score:
+ *   sum for max    every maximum of terms prev + post is m + log(sum exp(term - m)), m the largest term, in the order: a flip
+ *                  -- the stay, from flip b2 (if b2 != b), from flop b2 + 4 (at position 1: the stay, then the seven other
+ *                  states of position 0 ascending); a flop -- the stay, the step from flip b.  A single finite term is
+ *                  returned exactly; all -inf gives -inf, never NaN;
+ *   cleared band   a cell outside its block's band is -inf: when block t reads position p or p - 1 of the block before, a
+ *                  position outside the band of block t - 1 counts as -inf.  The score's parity buffers that are never
+ *                  cleared belong to the reference's Viterbi decoder; a sum over paths that reads a value of two blocks
+ *                  earlier again has no meaning.  The result is the weight of the paths that stay inside the band at every
+ *                  block; with the band off, the plain forward algorithm.
+ * Unlike the score this is a floating-point stage (expf and logf per cell), not bit for bit the definition: the device's
+ * error against reference_forward in float64 is held to at most twice the error of the definition's own float32
+ * restatement (the same term order, every addition rounded to float32; tests/test_gpu_trellis_forward.py). */
+int lva_forward_bases_device(lva_decoder *d, const float *post_dev, const int64_t *first_block, const int64_t *n_blocks,
+                             int32_t n_reads, const uint8_t *bases, const int64_t *first_base, const int32_t *n_bases,
+                             int32_t n_seqs, const int32_t *pairs, int32_t n_pairs, uint32_t max_deviation, float *out);
+int lva_forward_bases(lva_decoder *d, const float *post, const int64_t *row_offsets, int32_t n_reads, const uint8_t *bases,
+                      const int64_t *first_base, const int32_t *n_bases, int32_t n_seqs, const int32_t *pairs, int32_t n_pairs,
+                      uint32_t max_deviation, float *out);
 
 /* The traceback of the same trellis: WHERE the best path of a given base sequence runs on a read -- a segmentation of the
  * read (the block at which each base begins) and, for a truth that the band cut off, where its path left the band.  The

@@ -147,6 +147,8 @@ ABI = {
     "lva_align_profile": (_int, [_i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "lva_score_bases_device": (_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _u32, _vp]),
     "lva_score_bases": (_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _u32, _vp]),
+    "lva_forward_bases_device": (_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _u32, _vp]),
+    "lva_forward_bases": (_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _u32, _vp]),
     "lva_trace_bases_device": (_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _u32, _i32, _u64, _i32, _vp, _vp, _vp, _vp]),
     "lva_trace_bases": (_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _u32, _i32, _u64, _i32, _vp, _vp, _vp, _vp]),
     "lva_map_index_create_device": (_int, [_i32, _vp, _vp, _i32, _i32, _i32, ctypes.POINTER(_vp)]),

@@ -19,6 +19,7 @@
 #include "mp_kernels.h"
 #include "mq_kernels.h"
 #include "mi_kernels.h"
+#include "fw_kernels.h"
 #include "sc_kernels.h"
 #include "st_kernels.h"
 
@@ -1442,14 +1443,18 @@ uint64_t trace_bytes(uint32_t max_dev, int64_t nblk, int32_t n_bases) {
   return ((uint64_t)nblk * trace_width(max_dev, n_bases) + 15) & ~(uint64_t)15;
 }
 
+// which of the three answers of the one-message trellis a call asks for
+enum class ScoreKind { kScore, kForward, kTrace };
+
 // lva_score_bases (post on the host, read i = blocks [first_block[i], + n_blocks[i]) of it, T blocks in all: uploaded) and
-// lva_score_bases_device (post the caller's device buffer); with tr, lva_trace_bases and lva_trace_bases_device: the same
+// lva_score_bases_device (post the caller's device buffer); kForward, lva_forward_bases*: the same pairs, band tables, frame
+// and refusals, fw_forward in place of sc_score; kTrace (with tr), lva_trace_bases and lva_trace_bases_device: the same
 // pairs and band tables, st_fill and st_walk in place of sc_score, chunk by chunk of what the back-pointers may occupy
 int score_stage(lva_decoder* d, const float* post, size_t host_blocks, bool post_on_host, const int64_t* first_block,
                 const int64_t* n_blocks, int32_t n_reads, const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases,
                 int32_t n_seqs, const int32_t* pairs, int32_t n_pairs, uint32_t max_deviation, float* out,
-                const TraceOut* tr = nullptr) {
-  if (!d) return LVA_ERR_ARG;
+                ScoreKind kind = ScoreKind::kScore, const TraceOut* tr = nullptr) {
+  if (!d || (kind == ScoreKind::kTrace) != (tr != nullptr)) return LVA_ERR_ARG;
   int st = score_args(first_block, n_blocks, n_reads, bases, first_base, n_bases, n_seqs, pairs, n_pairs, post, out);
   if (st != LVA_OK) return st;
   const uint32_t max_dev = max_deviation == LVA_MAX_DEVIATION_DEFAULT ? d->max_dev : max_deviation;
@@ -1522,7 +1527,8 @@ int score_stage(lva_decoder* d, const float* post, size_t host_blocks, bool post
   const auto d_out = f.out(out, 2 * (size_t)n_pairs);
   if (!tr) {
     if ((st = f.begin()) != LVA_OK) return st;
-    const int e = launch_sc_score(post_on_host ? up.ptr() : post, w.bases, d_pairs, d_band, n_pairs, max_len, d_out, f.stream());
+    const auto launch = kind == ScoreKind::kForward ? launch_fw_forward : launch_sc_score;
+    const int e = launch(post_on_host ? up.ptr() : post, w.bases, d_pairs, d_band, n_pairs, max_len, d_out, f.stream());
     if (e) return launch_status(e);
     return f.finish();
   }
@@ -1570,13 +1576,32 @@ int lva_score_bases(lva_decoder* d, const float* post, const int64_t* row_offset
                      max_deviation, out);
 }
 
+int lva_forward_bases_device(lva_decoder* d, const float* post_dev, const int64_t* first_block, const int64_t* n_blocks, int32_t n_reads,
+                             const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases, int32_t n_seqs,
+                             const int32_t* pairs, int32_t n_pairs, uint32_t max_deviation, float* out) {
+  return score_stage(d, post_dev, 0, false, first_block, n_blocks, n_reads, bases, first_base, n_bases, n_seqs, pairs, n_pairs,
+                     max_deviation, out, ScoreKind::kForward);
+}
+
+int lva_forward_bases(lva_decoder* d, const float* post, const int64_t* row_offsets, int32_t n_reads, const uint8_t* bases,
+                      const int64_t* first_base, const int32_t* n_bases, int32_t n_seqs, const int32_t* pairs, int32_t n_pairs,
+                      uint32_t max_deviation, float* out) {
+  if (!d || n_reads < 0 || !row_offsets) return LVA_ERR_ARG;
+  size_t T = 0;
+  if (check_offsets(row_offsets, n_reads, &T) != LVA_OK) return LVA_ERR_ARG;
+  const std::vector<int32_t> len = read_lengths(row_offsets, n_reads);
+  const std::vector<int64_t> nb(len.begin(), len.end());
+  return score_stage(d, post, T, true, row_offsets, nb.data(), n_reads, bases, first_base, n_bases, n_seqs, pairs, n_pairs,
+                     max_deviation, out, ScoreKind::kForward);
+}
+
 int lva_trace_bases_device(lva_decoder* d, const float* post_dev, const int64_t* first_block, const int64_t* n_blocks, int32_t n_reads,
                            const uint8_t* bases, const int64_t* first_base, const int32_t* n_bases, int32_t n_seqs,
                            const int32_t* pairs, int32_t n_pairs, uint32_t max_deviation, int32_t end, uint64_t scratch_limit,
                            int32_t stride, float* out_score, int32_t* out_enter, uint8_t* out_kind, int32_t* out_info) {
   const TraceOut tr{end, scratch_limit, stride, out_enter, out_kind, out_info};
   return score_stage(d, post_dev, 0, false, first_block, n_blocks, n_reads, bases, first_base, n_bases, n_seqs, pairs, n_pairs,
-                     max_deviation, out_score, &tr);
+                     max_deviation, out_score, ScoreKind::kTrace, &tr);
 }
 
 int lva_trace_bases(lva_decoder* d, const float* post, const int64_t* row_offsets, int32_t n_reads, const uint8_t* bases,
@@ -1590,7 +1615,7 @@ int lva_trace_bases(lva_decoder* d, const float* post, const int64_t* row_offset
   const std::vector<int64_t> nb(len.begin(), len.end());
   const TraceOut tr{end, scratch_limit, stride, out_enter, out_kind, out_info};
   return score_stage(d, post, T, true, row_offsets, nb.data(), n_reads, bases, first_base, n_bases, n_seqs, pairs, n_pairs,
-                     max_deviation, out_score, &tr);
+                     max_deviation, out_score, ScoreKind::kTrace, &tr);
 }
 
 }  // extern "C"

@@ -371,6 +371,26 @@ class Decoder:
                 pr[flip == want, 1] = [at[m] for m in pr[flip == want, 1].tolist()]
         return seqs, pr
 
+    # --- the forward score of the same trellis (trellis_score.reference_forward is the definition; csrc/fw_kernels.hip) ---
+    def forward_bases(self, posts, seqs, pairs, max_deviation=None):
+        """The forward score of a base sequence on a read, per (read, sequence) pair: the log of the total weight of all
+        alignments inside the band, where score_bases gives the best one's; arguments and refusals as score_bases.
+        -> float32 [n_pairs, 2] = (flip, flop); trellis_score.forward_total adds the two.  A floating-point stage: within twice
+        the float32 restatement's error of trellis_score.reference_forward(posts[r], seqs[s], max_deviation), not its bits."""
+        flat, off = self._pack(posts)
+        return self._score(self._L.lva_forward_bases, (flat.ctypes.data, off.ctypes.data), len(off) - 1, seqs, pairs, max_deviation)
+
+    def forward_bases_resident(self, dev_ptr, first_block, n_blocks, seqs, pairs, max_deviation=None):
+        """forward_bases() on windows of a resident posterior buffer, as score_bases_resident reads them"""
+        fb = np.ascontiguousarray(first_block, dtype=np.int64)
+        nb = np.ascontiguousarray(n_blocks, dtype=np.int64)
+        return self._score(self._L.lva_forward_bases_device, (dev_ptr, fb.ctypes.data, nb.ctypes.data), len(fb), seqs, pairs,
+                           max_deviation)
+
+    def forward_messages(self, posts, msgs, pairs, rc=None):
+        """forward_bases() for messages under this decoder's code and max_deviation; msgs, pairs and rc as score_messages"""
+        return self.forward_bases(posts, *self._message_pairs(posts, msgs, pairs, rc))
+
     # --- the traceback of the same trellis (trellis_score.reference_trace is the definition; csrc/st_kernels.hip) --------
     def trace_bases(self, posts, seqs, pairs, max_deviation=None, end=-1, scratch_limit=0):
         """The best path of a base sequence on a read, per (read, sequence) pair; arguments as score_bases, end: the state of

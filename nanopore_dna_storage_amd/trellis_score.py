@@ -19,10 +19,17 @@ message, bit for bit (tests/test_trellis_score_host.py holds reference_score to 
   reference_trace   the definition of the traceback (csrc/st_kernels.hip): the best path of a sequence on a read, as the block
                     at which each position is entered; deviation_needed, left_band_at: what a band does to such a path;
   Decoder.trace_bases / trace_bases_resident / trace_messages   the same on the device, byte for byte;
+  reference_forward the definition of the forward score (csrc/fw_kernels.hip): the same trellis with a log-sum-exp for every
+                    maximum and every cell outside its block's band at -inf -- the log-weight of ALL alignments inside the
+                    band; forward_total, list_posterior, forward_order: the posterior of a list's entries given the read;
+  Decoder.forward_bases / forward_bases_resident / forward_messages   the same on the device, a float32 stage held to twice
+                    the error of the definition's float32 restatement;
   verdicts, main    the use: why did the list of a read miss the truth, and which max_deviation would have kept it?
+  list_rows         and: how much of the read's weight does each list entry hold, and which entry leads by likelihood?
 
     python -m nanopore_dna_storage_amd.trellis_score --simulate 2000 --seed 1 --mem_conv 11 --rate 5 --msg_len 180 \
-        --list_size 8 --max_deviation 20 --out run        # -> run.truth.tsv and a summary line; --trace: run.trace.tsv too
+        --list_size 8 --max_deviation 20 --out run        # -> run.truth.tsv and a summary line; --trace: run.trace.tsv too;
+                                                          #    --forward: fwd_truth, fwd_first, fwd_best, conf_first too
 """
 import argparse
 import sys
@@ -185,6 +192,106 @@ def reference_trace(post, bases, max_deviation, end=-1):
     return out
 
 
+def _lse(f, *terms):
+    """log-sum-exp of `terms` (arrays of dtype f, one shape) in their order: m + log(((e_1 + e_2) + ...) + e_k) with
+    e_i = exp(x_i - m), m the largest term; -inf where every term is -inf.  Every subtraction, addition and maximum is rounded
+    to f; exp and log are evaluated in float64 and rounded once (tests/transpost_ref.py, _lse32: numpy's float32 exp differs
+    from CPU to CPU).  The largest term's e is exactly 1 and a term of -inf adds exactly 0."""
+    with np.errstate(all="ignore"):
+        m = terms[0]
+        for x in terms[1:]:
+            m = np.maximum(m, x)
+        dead = np.isneginf(m)
+        mm = np.where(dead, f(0), m)
+        s = None
+        for x in terms:
+            e = np.exp((x - mm).astype(np.float64)).astype(f)
+            s = e if s is None else s + e
+        return np.where(dead, f(-np.inf), m + np.log(s.astype(np.float64)).astype(f))
+
+
+def reference_forward(post, bases, max_deviation, dtype=np.float64):
+    """The forward score (flip, flop) of the base sequence `bases` on a read: reference_score's trellis -- the same positions,
+    states, transitions, posterior entries, start (the eight states of position 0 at 0) and band_table -- with two differences:
+      sum for max   where reference_score takes the maximum of terms prev + post, this takes their log-sum-exp (_lse) in the
+                    order: a flip at p >= 2 -- the stay, from flip b2 (if b2 != b), from flop b2 + 4; a flip at p = 1 -- the
+                    stay, then the seven other states of position 0 ascending; a flop -- the stay, the step from flip b (if
+                    b2 = b or p = 1).  Position 0 only stays: a plain addition;
+      cleared band  a cell outside its block's band is -inf: when block t reads prev[p] or prev[p - 1], a position outside the
+                    band of block t - 1 counts as -inf (for t = 0, prev is the initial state).  reference_score's buffers
+                    that are never cleared belong to the reference's Viterbi decoder; a sum over paths that reads a value
+                    of two blocks earlier again has no meaning.
+    So the result is the log of the total weight of all alignments of the read to the sequence that stay inside the band at
+    every block; with the band off (max_deviation >= npos) the plain forward algorithm.  The definition of
+    csrc/fw_kernels.hip.  dtype float64 is the value; dtype float32 is the restatement the device is measured beside: the same
+    term order with every addition, subtraction and maximum rounded to float32 (the kernel follows this order).
+    Vectorised over the positions of a block: its cells depend on the block before alone.  Refuses what reference_score
+    refuses.  -> two scalars of dtype."""
+    f = np.dtype(dtype).type
+    if f not in (np.float64, np.float32):
+        raise ValueError("dtype is float64 (the value) or float32 (the restatement)")
+    post = np.ascontiguousarray(post, dtype=np.float32).reshape(-1, 40)
+    seq = as_codes(bases).astype(np.int64)
+    npos, nblk = len(seq) + 1, post.shape[0]
+    if len(seq) < 1:
+        raise ValueError("npos = len(bases) + 1, and at least one base")
+    if nblk < npos + 1:
+        raise ValueError("Too small post matrix: %d blocks for %d positions" % (nblk, npos))
+    if np.isnan(post).any() or np.isposinf(post).any():
+        raise ValueError("posteriors are finite or -inf")
+    neg = f(-np.inf)
+    post = post.astype(f)
+    stay = np.array([k * 8 + k for k in range(4)] + [32 + k for k in range(4, 8)])
+    bands = band_table(nblk, npos, max_deviation).tolist()
+    # per position p (index 0 unused): its base b, the base b2 below (p = 1 has none), and the posterior entries of its terms
+    b = np.concatenate([[0], seq])
+    b2 = np.concatenate([[0, 0], seq[:-1]])
+    same = b2 == b
+    i_stay, i_flip, i_flop, i_hold, i_step = b * 8 + b, b * 8 + b2, b * 8 + b2 + 4, 32 + b + 4, 32 + b
+    b1 = int(seq[0])
+    others = np.array([s for s in range(8) if s != b1])
+    zero = np.zeros(8, f)                                   # position 0, every state
+    flip, flop = np.full(npos, neg, f), np.full(npos, neg, f)    # [p] for p >= 1: flip b, flop b + 4; outside the band: -inf
+    for t in range(nblk):
+        row = post[t]
+        lo, hi = bands[t]
+        nzero, nflip, nflop = np.full(8, neg, f), np.full(npos, neg, f), np.full(npos, neg, f)
+        if lo == 0 and hi > 0:
+            nzero = zero + row[stay]
+        if lo <= 1 < hi:                                    # p = 1: every state of position 0
+            nflip[1] = _lse(f, flip[1] + row[b1 * 8 + b1], *(zero[others] + row[b1 * 8 + others]))
+            nflop[1] = _lse(f, flop[1] + row[32 + b1 + 4], zero[b1] + row[32 + b1])
+        a = max(lo, 2)
+        if a < hi:
+            p, q = slice(a, hi), slice(a - 1, hi - 1)       # the positions and the ones below
+            below = flip[q]
+            nflip[p] = _lse(f, flip[p] + row[i_stay[p]], np.where(same[p], neg, below) + row[i_flip[p]], flop[q] + row[i_flop[p]])
+            nflop[p] = _lse(f, flop[p] + row[i_hold[p]], np.where(same[p], below, neg) + row[i_step[p]])
+        zero, flip, flop = nzero, nflip, nflop
+    return f(flip[npos - 1]), f(flop[npos - 1])
+
+
+def forward_total(ff):
+    """float64 [n]: logaddexp(flip, flop) per row of forward scores [n, 2] -- the forward score of the sequence"""
+    ff = np.asarray(ff, dtype=np.float64).reshape(-1, 2)
+    return np.logaddexp(ff[:, 0], ff[:, 1])
+
+
+def list_posterior(totals):
+    """exp(totals - logsumexp(totals)): the posterior of each entry of one read's list given the read, restricted to the list.
+    Sums to 1; an entry with total -inf gets 0; all NaN if every total is -inf"""
+    totals = np.asarray(totals, dtype=np.float64).reshape(-1)
+    if not len(totals):
+        return totals.copy()
+    with np.errstate(invalid="ignore"):
+        return np.exp(totals - np.logaddexp.reduce(totals))
+
+
+def forward_order(totals):
+    """the entry indices by total descending, list order on ties"""
+    return np.argsort(-np.asarray(totals, dtype=np.float64).reshape(-1), kind="stable")
+
+
 def positions_after(enter, nblk):
     """int64 [nblk]: the position p_t at which a path stands after block t -- the number of positions with enter <= t"""
     enter = np.asarray(enter, dtype=np.int64)
@@ -285,14 +392,60 @@ def truth_rank(msgs, truth):
     return int(hit[0]) if len(hit) else -1
 
 
-def truth_rows(dec, dev, first_block, n_blocks, results, truth_msgs, rc):
+def _forward_totals(dec, dev, first_block, n_blocks, msgs_of, rc):
+    """One forward_bases_resident call under the decoder's band over (read, message) pairs: msgs_of[i] the messages (uint8
+    [k_i, msg_len], k_i may be 0) to weigh on read i, in the orientation of its rc flag -> [float64 [k_i]], forward_total of
+    each.  A read with fewer blocks than the code's positions + 1 is not paired: its totals are empty."""
+    n = len(msgs_of)
+    sync = (dec._sync.decode() if dec._sync else "", dec._sync_period)
+    info = _dec.code_info(dec.mem_conv, dec.rate, dec.msg_len, False, *sync)
+    rc = np.zeros(n, bool) if rc is None else np.asarray(rc, dtype=bool)
+    seqs, pairs, at = [], [], []
+    for i in range(n):
+        k = len(msgs_of[i]) if int(n_blocks[i]) >= info.nstate_pos + 1 else 0
+        at.append((len(seqs), k))
+        if k:
+            enc = message_bases(dec.mem_conv, dec.rate, dec.msg_len, np.asarray(msgs_of[i], np.uint8), bool(rc[i]), *sync)
+            pairs += [(i, len(seqs) + j) for j in range(k)]
+            seqs += list(enc)
+    if not pairs:
+        return [np.zeros(0) for _ in range(n)]
+    tot = forward_total(dec.forward_bases_resident(dev, first_block, n_blocks, seqs, pairs))
+    return [tot[a:a + k] for a, k in at]
+
+
+def _entries(res, msg_len):
+    """the messages of a decode result as uint8 [count, msg_len]; an error code or an empty list: no rows"""
+    msgs = () if isinstance(res, int) else res[0]
+    return np.asarray(msgs, np.uint8).reshape(-1, msg_len) if len(msgs) else np.zeros((0, msg_len), np.uint8)
+
+
+def _list_row(totals):
+    return dict(totals=totals, posterior=list_posterior(totals), order=forward_order(totals))
+
+
+def list_rows(dec, dev, first_block, n_blocks, results, rc):
+    """The forward score of every entry of every decoded list, in ONE forward_bases_resident call over (read, entry) pairs on
+    the buffer the decode read, under the decoder's band.  Per read -> dict(totals float64 [count]: forward_total of each
+    entry; posterior: list_posterior(totals), the weight of each entry given the read, restricted to the list; order:
+    forward_order(totals), the entries by likelihood).  A read whose decode returned an error code, an empty list or that is a
+    short_read gets empty arrays."""
+    tot = _forward_totals(dec, dev, first_block, n_blocks, [_entries(r, dec.msg_len) for r in results], rc)
+    return [_list_row(t) for t in tot]
+
+
+def truth_rows(dec, dev, first_block, n_blocks, results, truth_msgs, rc, forward=False):
     """The table of the tool for reads that are resident on the device (windows first_block / n_blocks of the buffer `dev`),
     their decode results and their true messages: two score_bases_resident calls on the buffer the decode read, one under the
     decoder's band and one with the band off, and one trace_bases_resident call with the band off -- where the truth's best
     path runs.  -> [dict(rank, banded, unbanded, first, last, verdict, dev_needed, left_band_at, trace)]: dev_needed the
     smallest max_deviation whose band holds that path (deviation_needed; nan for a short read and a truth without a path),
     left_band_at the first block at which the path lies outside the decoder's band or -1, trace = dict(start_state,
-    end_state, enter) of the path or None."""
+    end_state, enter) of the path or None.
+    forward: one forward_bases_resident call more, over every list entry and the truth of every read under the decoder's
+    band, and four keys more per row: fwd_truth (the truth's forward total; nan for a short read), fwd_first (the total of the
+    list's first entry; nan for no list), fwd_best (the list place of the entry with the largest total, -1 for no list) and
+    conf_first (the posterior of the first entry, list_posterior; nan for no list)."""
     n = len(results)
     sync = (dec._sync.decode() if dec._sync else "", dec._sync_period)
     info = _dec.code_info(dec.mem_conv, dec.rate, dec.msg_len, False, *sync)
@@ -322,6 +475,16 @@ def truth_rows(dec, dev, first_block, n_blocks, results, truth_msgs, rc):
                          last=float(scores[-1]) if len(scores) else float("nan"),
                          verdict=verdict(rank, banded.get(i), unbanded.get(i), scores, dec.list_size),
                          **path.get(i, dict(dev_needed=float("nan"), left_band_at=-1, trace=None))))
+    if forward:                                              # the lists and the truths in one call: the truth last per read
+        truth = np.asarray(truth_msgs, np.uint8).reshape(n, dec.msg_len)
+        both = [np.concatenate([_entries(res, dec.msg_len), truth[i:i + 1]]) for i, res in enumerate(results)]
+        for row, tot in zip(rows, _forward_totals(dec, dev, first_block, n_blocks, both, rc)):
+            lst = _list_row(tot[:-1])
+            have = len(lst["totals"]) > 0
+            row.update(fwd_truth=float(tot[-1]) if len(tot) else float("nan"),
+                       fwd_first=float(lst["totals"][0]) if have else float("nan"),
+                       fwd_best=int(lst["order"][0]) if have else -1,
+                       conf_first=float(lst["posterior"][0]) if have else float("nan"))
     return rows
 
 
@@ -329,26 +492,31 @@ def count_verdicts(rows):
     return {v: sum(r["verdict"] == v for r in rows) for v in VERDICTS}
 
 
-def simulate_rows(dec, n, seed, first_read=0, **kw):
+def simulate_rows(dec, n, seed, first_read=0, forward=False, **kw):
     """Decoder.simulate_and_decode with the truth scored on the buffer the decode read, before it is freed: the reads never
-    leave the device -> (truth, results, rows)"""
+    leave the device -> (truth, results, rows); forward: truth_rows' flag"""
     def after(dev, off, truth, results, rc):
-        return truth_rows(dec, dev, off[:-1], np.diff(off), results, truth["msgs"], rc)
+        return truth_rows(dec, dev, off[:-1], np.diff(off), results, truth["msgs"], rc, forward=forward)
     return dec.simulate_and_decode(n, seed, first_read, after=after, **kw)
 
 
 def write_table(rows, path):
     """P.truth.tsv: the seven columns of the scores, and after them dev_needed and left_band_at where the rows carry the trace
-    of the truth (truth_rows' do)"""
+    of the truth (truth_rows' do), and after those fwd_truth, fwd_first, fwd_best and conf_first where the rows carry the forward
+    scores (truth_rows(forward=True))"""
     traced = bool(rows) and all("dev_needed" in r for r in rows)
+    fwd = bool(rows) and all("fwd_best" in r for r in rows)
     with open(path, "w") as f:
-        f.write("read\trank\tbanded\tunbanded\tfirst\tlast\tverdict" + ("\tdev_needed\tleft_band_at" if traced else "") + "\n")
+        f.write("read\trank\tbanded\tunbanded\tfirst\tlast\tverdict" + ("\tdev_needed\tleft_band_at" if traced else "")
+                + ("\tfwd_truth\tfwd_first\tfwd_best\tconf_first" if fwd else "") + "\n")
         for i, r in enumerate(rows):
             sc = lambda v: "nan" if v is None else repr(float(v))
             f.write("%d\t%d\t%s\t%s\t%r\t%r\t%s" % (i, r["rank"], sc(r["banded"]), sc(r["unbanded"]), r["first"], r["last"],
                                                   r["verdict"]))
             if traced:
                 f.write("\t%s\t%d" % ("nan" if r["dev_needed"] != r["dev_needed"] else "%d" % r["dev_needed"], r["left_band_at"]))
+            if fwd:
+                f.write("\t%r\t%r\t%d\t%r" % (r["fwd_truth"], r["fwd_first"], r["fwd_best"], r["conf_first"]))
             f.write("\n")
 
 
@@ -370,11 +538,20 @@ def band_dev_needed(rows):
     return int(max(need)) if need else 0
 
 
-def summary_line(rows, dev_needed=False):
-    """the count per verdict; dev_needed: and the largest dev_needed among the reads with verdict band (band_dev_needed)"""
+def forward_counts(rows):
+    """(reads whose list is led by another entry by forward total than by best path: fwd_best > 0; reads whose truth is in the
+    list, not first by best path, and first by forward total: rank > 0 and fwd_best == rank) of rows that carry the forward
+    scores"""
+    return sum(r["fwd_best"] > 0 for r in rows), sum(r["rank"] > 0 and r["fwd_best"] == r["rank"] for r in rows)
+
+
+def summary_line(rows, dev_needed=False, forward=False):
+    """the count per verdict; dev_needed: and the largest dev_needed among the reads with verdict band (band_dev_needed);
+    forward: and forward_counts"""
     c = count_verdicts(rows)
     line = "truth score: %d reads, " % len(rows) + ", ".join("%s %d" % (v, c[v]) for v in VERDICTS)
-    return line + (", band dev_needed %d" % band_dev_needed(rows) if dev_needed else "")
+    line += ", band dev_needed %d" % band_dev_needed(rows) if dev_needed else ""
+    return line + (", fwd_best != 0 %d, truth first by forward only %d" % forward_counts(rows) if forward else "")
 
 
 def build_parser():
@@ -394,6 +571,10 @@ def build_parser():
     p.add_argument("--trace", action="store_true",
                    help="also write P.trace.tsv (the truth's unbanded path per read: start_state, end_state, the block at which "
                         "each position is entered) and add the largest dev_needed among the band reads to the summary line")
+    p.add_argument("--forward", action="store_true",
+                   help="also weigh every list entry and the truth by ALL their alignments (the forward score): four columns "
+                        "more in P.truth.tsv (fwd_truth, fwd_first, fwd_best, conf_first), and in the summary line the reads "
+                        "with fwd_best != 0 and those whose truth is in the list, not first by best path, first by forward total")
     p.add_argument("--manifest", help="a text file, one read per line: <posterior file (.post)> <true message as 0/1> [rc: 0/1]")
     return p
 
@@ -406,7 +587,7 @@ def main(argv=None, out=sys.stdout):
                       device=args.device) as dec:
         if args.simulate:
             kw = {k: getattr(args, k) for k in ("sub", "dele", "ins") if getattr(args, k) is not None}
-            _, _, rows = simulate_rows(dec, args.simulate, args.seed, **kw)
+            _, _, rows = simulate_rows(dec, args.simulate, args.seed, forward=args.forward, **kw)
         else:
             posts, msgs, rc = [], [], []
             for ln in open(args.manifest):
@@ -418,11 +599,12 @@ def main(argv=None, out=sys.stdout):
                 rc.append(len(w) > 2 and w[2] == "1")
             with dec.resident(posts) as (dev, off):
                 results = dec.decode_resident(dev, off, rc)
-                rows = truth_rows(dec, dev, off[:-1], np.diff(off), results, np.array(msgs, dtype=np.uint8), rc)
+                rows = truth_rows(dec, dev, off[:-1], np.diff(off), results, np.array(msgs, dtype=np.uint8), rc,
+                                  forward=args.forward)
     write_table(rows, args.out + ".truth.tsv")
     if args.trace:
         write_trace(rows, args.out + ".trace.tsv")
-    print(summary_line(rows, dev_needed=args.trace), file=out)
+    print(summary_line(rows, dev_needed=args.trace, forward=args.forward), file=out)
     return 0
 
 
