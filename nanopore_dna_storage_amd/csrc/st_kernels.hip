@@ -1,14 +1,14 @@
 // st_kernels.hip -- DESIGN.md section 1 row N7, the traceback: the best path of a given base sequence on a read.
 //
 // The definition is trellis_score.reference_trace; the device is held to it byte for byte (tests/test_gpu_trellis_trace.py).
-// The forward pass is sc_score's (sc_kernels.hip, which stays as it is: one kernel, measured as such), restated here with
-// the one thing a traceback adds -- which predecessor won.  The tie rule is the one sc_score's hi_of chain implies: a later
-// candidate replaces an earlier one only if it is strictly greater, the candidates in the kernel's order (stay first, then
-// the states of the position below, ascending; for a flop the stay, then the step).
+// The forward pass is the frame that sc_score runs (sc_frame.h) under a cell rule that adds the one thing a traceback
+// needs -- which predecessor won.  The tie rule is the one sc_score's hi_of chain implies: a later candidate replaces an
+// earlier one only if it is strictly greater, the candidates in the frame's order (stay first, then the states of the
+// position below, ascending; for a flop the stay, then the step).
 //
-//   st_fill   sc_score's forward pass, same structure, same LDS, same additions: the two end scores are sc_score's bits.
-//             For every cell it writes it stores one back-pointer byte (st_kernels.h) to the pair's scratch in HBM,
-//             [nblk][w] indexed by p - lo(t): consecutive lanes store consecutive bytes.
+//   st_fill   sc_frame under StRule: same LDS, same additions, the maxima as compare and select, so the two end scores are
+//             sc_score's bits.  For every cell it writes it stores one back-pointer byte (st_kernels.h) to the pair's
+//             scratch in HBM, [nblk][w] indexed by p - lo(t): consecutive lanes store consecutive bytes.
 //   st_walk   the traceback, one wavefront per pair, in runs of kStRun blocks: the 64 lanes stage the kStRun bytes of each
 //             row that the walk can reach (it moves down at most one position per block) and the band words of the run
 //             into LDS -- one byte per lane and row, consecutive lanes consecutive bytes, the loads of a run in flight
@@ -19,102 +19,57 @@
 // Two kernels, not a tail: the walk wants other LDS (staged rows, not parity buffers) and other registers than the fill,
 // whose register figure is what keeps eight wavefronts on a SIMD; launched on one stream the second sees the first's stores.
 //
-// LDS ordering in st_fill is sc_score's (see there).  In st_walk a barrier separates a run's staging stores from its walk
-// and the walk's loads from the next run's staging; control flow around both is uniform.
+// LDS ordering in st_fill is the frame's (sc_frame.h); StRule stores to HBM only.  In st_walk a barrier separates a run's
+// staging stores from its walk and the walk's loads from the next run's staging; control flow around both is uniform.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "sc_frame.h"
 #include "st_kernels.h"
 
 namespace lva {
 
 namespace {
 
-constexpr float kNegInf = -__builtin_huge_valf();
+// ScRule's maxima with the winner kept, and the byte of every cell stored after it
+struct StRule : ScRule {
+  uint8_t* back;          // the pair's back-pointers, [nblk][w]
+  uint32_t w;
+  uint8_t* brow;          // brow[p - lo]: the byte of position p of this block
+  uint32_t won, in;       // of the cell at hand: the flip's choice, the flop's bit
+
+  __device__ StRule(uint8_t* back, uint32_t w) : back(back), w(w), brow(back), won(0), in(0) {}
+  __device__ float flip_first(float stay, const float (&x)[8], uint32_t b) {
+    float flip = stay;
+    won = 0;
+#pragma unroll
+    for (uint32_t s = 0; s < 8; ++s)
+      if (s != b && flip < x[s]) { flip = x[s]; won = 1 + s; }
+    return flip;
+  }
+  __device__ float flip_of(float stay, float from_flip, float from_flop, uint32_t b2) {
+    float flip = stay;
+    won = 0;
+    if (flip < from_flip) { flip = from_flip; won = 1 + b2; }
+    if (flip < from_flop) { flip = from_flop; won = 5 + b2; }
+    return flip;
+  }
+  __device__ float flop_of(float stay, float step) {
+    in = stay < step ? kStFlopBit : 0u;
+    return in ? step : stay;
+  }
+  __device__ void block_begins(int t) { brow = back + (size_t)t * w; }
+  __device__ void stored(int p, int lo) const { brow[p - lo] = (uint8_t)(p == 0 ? 0u : won | in); }   // position 0 only stays
+};
 
 // grid = pairs, block = one wavefront; dynamic LDS: sc_lds_bytes(max_len), cap = sc_lds_positions(max_len)
 __global__ __launch_bounds__(64) void st_fill(const float* __restrict__ post, const uint8_t* __restrict__ bases,
                                               const ScPair* __restrict__ pairs, const StBp* __restrict__ bp,
                                               const uint32_t* __restrict__ band, int cap, uint8_t* __restrict__ scratch,
                                               float* __restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* stage = reinterpret_cast<float*>(smem);                        // [kScStage][40]
-  float* zero = stage + kScStage * 40;                                  // [2][8]: position 0, every state
-  float2* st = reinterpret_cast<float2*>(zero + 16);                    // [2][cap]: (flip b, flop b + 4) of position p >= 1
-  uint8_t* bb = reinterpret_cast<uint8_t*>(st + 2 * (size_t)cap);       // [cap]: base of p | base of p - 1 << 2
-
-  const int lane = threadIdx.x;
-  const ScPair pr = pairs[blockIdx.x];
   const StBp where = bp[blockIdx.x];
-  const int npos = (int)pr.len + 1, nblk = (int)pr.nblk;
-  uint8_t* back = scratch + where.at;
-
-  for (int p = lane; p < npos; p += 64) {
-    st[p] = make_float2(kNegInf, kNegInf);
-    st[cap + p] = make_float2(kNegInf, kNegInf);
-    const uint32_t b = p >= 1 ? base_code(bases[pr.seq_off + p - 1]) & 3u : 0u;
-    const uint32_t b2 = p >= 2 ? base_code(bases[pr.seq_off + p - 2]) & 3u : 0u;
-    bb[p] = (uint8_t)(b | b2 << 2);
-  }
-  if (lane < 8) { zero[lane] = 0.0f; zero[8 + lane] = kNegInf; }
-
-  const float* rows = post + (size_t)pr.row0 * 40;
-  for (int t0 = 0; t0 < nblk; t0 += kScStage) {
-    const int nrows = min(kScStage, nblk - t0);
-    for (int i = lane; i < nrows * 40; i += 64) stage[i] = rows[(size_t)t0 * 40 + i];
-    const uint32_t my_band = lane < nrows ? band[pr.band_at + t0 + lane] : 0u;
-    __syncthreads();
-    for (int u = 0; u < nrows; ++u) {
-      const uint32_t bw = __builtin_amdgcn_readlane(my_band, u);
-      const int lo = (int)(bw & 0xFFFFu), hi = (int)(bw >> 16);
-      const int from = ((t0 + u) & 1), to = from ^ 1;
-      const float* row = stage + u * 40;
-      const float2* prev = st + (size_t)from * cap;
-      float2* cur = st + (size_t)to * cap;
-      const float* zprev = zero + from * 8;
-      uint8_t* brow = back + (size_t)(t0 + u) * where.w;                 // brow[p - lo]: the byte of position p of this block
-      for (int p = lo + lane; p < hi; p += 64) {
-        if (p == 0) {                                                   // stays only
-          float* zcur = zero + to * 8;
-#pragma unroll
-          for (int k = 0; k < 8; ++k) zcur[k] = zprev[k] + row[k < 4 ? k * 8 + k : 32 + k];
-          brow[0] = 0;                                                  // (p == 0 is in the band: lo == 0)
-          continue;
-        }
-        const uint32_t c = bb[p], b = c & 3u, b2 = (c >> 2) & 3u;
-        const float2 me = prev[p];
-        float flip = me.x + row[b * 8 + b], step;
-        uint32_t won = 0;
-        if (p == 1) {                                                   // from every state of position 0 but flip b
-#pragma unroll
-          for (uint32_t s = 0; s < 8; ++s)
-            if (s != b) {
-              const float v = zprev[s] + row[b * 8 + s];
-              if (flip < v) { flip = v; won = 1 + s; }
-            }
-          step = zprev[b];
-        } else {
-          const float2 below = prev[p - 1];
-          const float v = (b2 != b ? below.x : kNegInf) + row[b * 8 + b2];
-          if (flip < v) { flip = v; won = 1 + b2; }
-          const float w = below.y + row[b * 8 + b2 + 4];
-          if (flip < w) { flip = w; won = 5 + b2; }
-          step = b2 == b ? below.x : kNegInf;
-        }
-        const float held = me.y + row[32 + b + 4], stepped = step + row[32 + b];
-        const bool in = held < stepped;
-        cur[p] = make_float2(flip, in ? stepped : held);
-        brow[p - lo] = (uint8_t)(won | (in ? kStFlopBit : 0u));
-      }
-      __syncthreads();
-    }
-  }
-  if (lane == 0) {
-    const float2 r = st[(size_t)(nblk & 1) * cap + npos - 1];
-    out[(size_t)blockIdx.x * 2] = r.x;
-    out[(size_t)blockIdx.x * 2 + 1] = r.y;
-  }
+  sc_frame(post, bases, pairs, band, cap, out, StRule(scratch + where.at, where.w));
 }
 
 __device__ inline uint32_t first_lane(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }

@@ -13,7 +13,8 @@ block's band keeps what it held two blocks earlier, and the reference reads it a
 lists of tests/golden/m8_r3_L8_edge*).  Every score of a decoded list is one of the two values this returns for the listed
 message, bit for bit (tests/test_trellis_score_host.py holds reference_score to the oracle on that).
 
-  reference_score   the definition, plain numpy (this file is to csrc/sc_kernels.hip what read_map.py is to mp_kernels.hip);
+  reference_score   the definition, plain numpy (this file is to csrc/sc_kernels.hip what read_map.py is to mp_kernels.hip;
+                    the three kernels are one frame, csrc/sc_frame.h, under three cell rules -- the definitions stay three);
   message_bases     the base sequence that a decode with a given rc flag walks for a message;
   Decoder.score_bases / score_bases_resident / score_messages (decoder.py)   the same on the device, bit for bit;
   reference_trace   the definition of the traceback (csrc/st_kernels.hip): the best path of a sequence on a read, as the block
@@ -59,6 +60,22 @@ def band_table(nblk, npos, max_deviation):
     return np.array([_band(t, nblk, npos, int(max_deviation)) for t in range(nblk)], dtype=np.int64).reshape(nblk, 2)
 
 
+def _trellis_inputs(post, bases, max_deviation):
+    """What the three definitions below start from, and what they refuse (ValueError): post as float32 [nblk, 40], the base
+    codes, npos = len(bases) + 1, nblk, the posterior index of every state's stay at position 0, band_table"""
+    post = np.ascontiguousarray(post, dtype=np.float32).reshape(-1, 40)
+    seq = as_codes(bases)
+    npos, nblk = len(seq) + 1, post.shape[0]
+    if len(seq) < 1:
+        raise ValueError("npos = len(bases) + 1, and at least one base")
+    if nblk < npos + 1:
+        raise ValueError("Too small post matrix: %d blocks for %d positions" % (nblk, npos))
+    if np.isnan(post).any() or np.isposinf(post).any():
+        raise ValueError("posteriors are finite or -inf")
+    stay = np.array([k * 8 + k for k in range(4)] + [32 + k for k in range(4, 8)])
+    return post, seq, npos, nblk, stay, band_table(nblk, npos, max_deviation)
+
+
 def reference_score(post, bases, max_deviation, npos=None):
     """The two scores (flip, flop; float32) with which the reference trellis ends on the base sequence `bases` (uint8 codes
     0..3, or the characters ACGT) for a read of posteriors `post` (float32 [nblk, 40], .post layout).
@@ -76,21 +93,12 @@ def reference_score(post, bases, max_deviation, npos=None):
     above 3.  Posteriors are finite or -inf: NaN and +inf are outside the definition (the reference's heap and its
     `!= -inf` tests give them a meaning that depends on the list size; tests/golden/*_nan*, *_posinf* pin the decoder there,
     not this function)."""
-    post = np.ascontiguousarray(post, dtype=np.float32).reshape(-1, 40)
-    seq = as_codes(bases)
-    if npos is None:
-        npos = len(seq) + 1
-    if npos != len(seq) + 1 or len(seq) < 1:
+    given = npos
+    post, seq, npos, nblk, stay, bands = _trellis_inputs(post, bases, max_deviation)
+    if given is not None and given != npos:
         raise ValueError("npos = len(bases) + 1, and at least one base")
-    nblk = post.shape[0]
-    if nblk < npos + 1:
-        raise ValueError("Too small post matrix: %d blocks for %d positions" % (nblk, npos))
-    if np.isnan(post).any() or np.isposinf(post).any():
-        raise ValueError("posteriors are finite or -inf")
     buf = np.full((2, npos, 8), NEG, dtype=np.float32)
     buf[0, 0, :] = 0
-    stay = np.array([k * 8 + k for k in range(4)] + [32 + k for k in range(4, 8)])
-    bands = band_table(nblk, npos, max_deviation)
     for t in range(nblk):
         prev, cur = buf[t & 1], buf[(t + 1) & 1]
         row = post[t]
@@ -129,19 +137,9 @@ def reference_trace(post, bases, max_deviation, end=-1):
     Refuses what reference_score refuses, and an end outside -1..1."""
     if end not in (-1, 0, 1):
         raise ValueError("end is 0 (flip), 1 (flop) or -1 (the larger)")
-    post = np.ascontiguousarray(post, dtype=np.float32).reshape(-1, 40)
-    seq = as_codes(bases)
-    npos, nblk = len(seq) + 1, post.shape[0]
-    if len(seq) < 1:
-        raise ValueError("at least one base")
-    if nblk < npos + 1:
-        raise ValueError("Too small post matrix: %d blocks for %d positions" % (nblk, npos))
-    if np.isnan(post).any() or np.isposinf(post).any():
-        raise ValueError("posteriors are finite or -inf")
+    post, seq, npos, nblk, stay, bands = _trellis_inputs(post, bases, max_deviation)
     buf = np.full((2, npos, 8), NEG, dtype=np.float32)
     buf[0, 0, :] = 0
-    stay = np.array([k * 8 + k for k in range(4)] + [32 + k for k in range(4, 8)])
-    bands = band_table(nblk, npos, max_deviation)
     won = np.zeros((nblk, npos, 2), np.uint8)              # [t, p] = (flip: 0 stay, 1 + s from state s; flop: 0 stay, 1 step)
     for t in range(nblk):
         prev, cur = buf[t & 1], buf[(t + 1) & 1]
@@ -230,19 +228,9 @@ def reference_forward(post, bases, max_deviation, dtype=np.float64):
     f = np.dtype(dtype).type
     if f not in (np.float64, np.float32):
         raise ValueError("dtype is float64 (the value) or float32 (the restatement)")
-    post = np.ascontiguousarray(post, dtype=np.float32).reshape(-1, 40)
-    seq = as_codes(bases).astype(np.int64)
-    npos, nblk = len(seq) + 1, post.shape[0]
-    if len(seq) < 1:
-        raise ValueError("npos = len(bases) + 1, and at least one base")
-    if nblk < npos + 1:
-        raise ValueError("Too small post matrix: %d blocks for %d positions" % (nblk, npos))
-    if np.isnan(post).any() or np.isposinf(post).any():
-        raise ValueError("posteriors are finite or -inf")
+    post, seq, npos, nblk, stay, bands = _trellis_inputs(post, bases, max_deviation)
     neg = f(-np.inf)
-    post = post.astype(f)
-    stay = np.array([k * 8 + k for k in range(4)] + [32 + k for k in range(4, 8)])
-    bands = band_table(nblk, npos, max_deviation).tolist()
+    post, seq, bands = post.astype(f), seq.astype(np.int64), bands.tolist()
     # per position p (index 0 unused): its base b, the base b2 below (p = 1 has none), and the posterior entries of its terms
     b = np.concatenate([[0], seq])
     b2 = np.concatenate([[0, 0], seq[:-1]])

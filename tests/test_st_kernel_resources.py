@@ -1,9 +1,9 @@
 """What the gfx950 code object of the traceback kernels must keep (no GPU needed: hipcc cross-compiles), after
 tests/test_sc_kernel_resources.py.  csrc/st_kernels.hip holds st_fill and st_walk; nothing is in scratch memory; st_fill, which
-is sc_score's forward pass with a byte store per cell, stays within 64 vector registers (eight wavefronts per SIMD hide its
-chain of dependent LDS round trips) and st_walk too; all LDS is dynamic -- st_fill's is sc_score's formula, st_walk's a run
-of kStRun rows of kStRun bytes and their band words -- and the arithmetic is add and compare/select, no FMA.
-csrc/sc_kernels.hip still holds sc_score alone."""
+is the frame sc_score runs (csrc/sc_frame.h) with a byte store per cell, stays within 64 vector registers (eight wavefronts
+per SIMD hide its chain of dependent LDS round trips) and st_walk too; all LDS is dynamic -- st_fill's is sc_score's formula,
+st_walk's a run of kStRun rows of kStRun bytes and their band words -- and the arithmetic is add and compare/select, no FMA.
+The shared frame is a function, not a kernel: csrc/sc_kernels.hip still compiles to sc_score alone."""
 import os
 import re
 import subprocess
